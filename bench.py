@@ -12,10 +12,16 @@ NMS/top-k decode + 2D->3D postProcess (one gather launch) -> (N>1) RCCL all-gath
 configs[1]: Centerfusion_Middle, bs=16 per GPU, 3x448x800, <=200-point synthetic radar sweeps,
 random-init weights (no network for checkpoints).  Weak scaling: every rank runs its own 16 frames.
 
-Prints ONE JSON line on rank 0 (see the task contract); `roofline` is the dominant kernel
-(head_patch_kernel: the 7 primary and the 4 secondary heads, 3x3 conv + 1x1 chain each in one launch,
-58 % of all FLOPs, a third of the step) timed with HIP events on the launch stream; `cpu_baseline` is
-the CPU oracle (a port, not the reference) timed on this host on a bounded sample.
+Prints ONE JSON line on rank 0: `value` (frames/s), `ms_per_step` (wall time of one timed step; the MAX over
+ranks), the step distribution and every rank's diagnostics.  A plain run does nothing else: set up, `--warmup`
+steps, `--steps` timed steps, the line.  `--dump-outputs DIR` writes the last timed step's result (the gathered
+postProcess rows) to DIR/post.npy; inputs and weights are seeded, so equal arguments give equal inputs.
+
+`--full` adds the rest: `roofline` is the dominant kernel (head_patch_kernel: the 7 primary and the 4 secondary
+heads, 3x3 conv + 1x1 chain each in one launch, 58 % of all FLOPs, a third of the step) timed with HIP events on
+the launch stream; `roofline_gather` the DCN gather layers, timed in a few steps of their own; on one GPU
+`other_configs` (the other BASELINE configurations, default shape only) and `cpu_baseline`, the CPU oracle (a
+port, not the reference) timed on this host on a bounded sample (`--no-cpu-baseline` skips both).
 """
 import argparse
 import json
@@ -244,6 +250,8 @@ def end_to_end(args, dev, model):
             post = step()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"post": post})
         # resident-input floor of the same step (inputs already pre-processed on the device): the pipelined chain cannot
         # beat it
         images, pc_dep, metas, calibs = det.pre_process(frames, infos, sweeps)
@@ -458,6 +466,23 @@ class StepClock:
                 for r, o in enumerate(out)]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: tensor} -> out_dir/<name>.npy (float64 stays float64, everything else float32).  An output that would
+    take the files past DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of its leading-axis rows (sorted)."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.nbytes > budget:
+            keep = max(1, budget // max(1, a[:1].nbytes))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def free_port():
     import socket
     with socket.socket() as so:
@@ -602,7 +627,17 @@ def main():
                          "bottleneck; on one GPU eager launches are as fast: DESIGN.md section 3)")
     ap.add_argument("--end-to-end", action="store_true",
                     help="print the Detector.run-shaped line instead (uint8 frames + raw radar over PCIe -> final boxes)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the dominant kernel's roofline (HIP events on its launches "
+                         "inside the timed steps) and the DCN gather roofline (a few steps of its own); on one GPU also the "
+                         "other BASELINE configurations (default shape only) and the CPU oracle baseline (unless "
+                         "--no-cpu-baseline).  Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the gathered postProcess rows, "
+                         f"(B x n_gpus, 100, 54)) as DIR/post.npy, float32, at most {DUMP_LIMIT_BYTES >> 20} MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # started bare (`python bench.py --gpus N`): become the launcher.  This process has not touched the GPU (and
@@ -647,6 +682,7 @@ def main():
     from centerfusiondetect3d_amd.postprocess import inverse_affine_device
     assume_equal_shards(True)
     B, H, W = args.batch, args.height, args.width
+    torch.manual_seed(0)             # the default init of the weights synthetic_weights leaves alone: equal arguments, equal outputs
     model = getModel(centerfusion_middle_config((H, W)))
     if args.exact_fp32:
         model.conv_f16 = False
@@ -720,8 +756,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # exact-fp32 build: the heads are unfused fp32-MFMA convolutions; its dominant launches are the two first layers
-    dominant = ["heads.primary.0", "heads.secondary.0"] if args.exact_fp32 else DOMINANT
+    # exact-fp32 build: the heads are unfused fp32-MFMA convolutions; its dominant launches are the two first layers.
+    # Only --full times them (HIP events on those launches inside the timed steps).
+    dominant = (["heads.primary.0", "heads.secondary.0"] if args.exact_fp32 else DOMINANT) if args.full else []
     with torch.no_grad():
         for _ in range(args.warmup):
             step()
@@ -737,7 +774,9 @@ def main():
         fence()
         dt = time.perf_counter() - t0
         clock.on = False
-    if args.use_graph:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"post": det})     # before any later step can reuse a buffer
+    if args.use_graph and args.full:
         # a graph replay has no per-launch events: the dominant kernel is timed in three eager steps behind the timed region
         model.use_graph = False
         with torch.no_grad():
@@ -761,7 +800,7 @@ def main():
     # pixel through the L2 -> TA path.  Timed with HIP events on their launch streams in a few steps BEHIND the timed region
     # (20 more event pairs per step would sit inside `value` otherwise).
     gather = None
-    if not args.exact_fp32 and not args.use_graph:
+    if args.full and not args.exact_fp32 and not args.use_graph:
         with torch.no_grad():
             for name in GATHER_LAYERS:
                 model.time_launch(name, True)
@@ -786,10 +825,6 @@ def main():
 
     if rank == 0:
         fps = world * B * args.steps / dt
-        avg_ms = float(np.mean(launch_ms))
-        launch_flops = launch_flops / len(launch_ms)          # algorithmic FLOPs of an average launch
-        achieved = launch_flops / (avg_ms * 1e-3) / 1e12
-        peak = FP32_MFMA_PEAK_TFLOPS if args.exact_fp32 else BF16_MFMA_PEAK_TFLOPS
         result = {
             "metric": METRIC, "value": round(fps, 2), "unit": "frames/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -808,23 +843,28 @@ def main():
             **{k: max(r[k] for r in ranks) for k in ("step_ms_p50", "step_ms_p95", "step_ms_max")},
             "ranks": ranks,
             "model_tflops": round(fps * GFLOP_PER_FRAME * (H * W) / (448 * 800) / 1e3, 2),
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak,
-                         "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-                         "traffic": None if args.exact_fp32 else measured_traffic(),
-                         "kernel": ("conv_igemm_kernel (fp32 MFMA; the 3x3 first layers of the 7 primary / 4 secondary heads)"
-                                    if args.exact_fp32 else
-                                    "head_patch16_kernel (cf_head_fused, v_mfma_f32_16x16x32_bf16; 2 launches/step: 7 primary heads, 4 secondary heads)"
-                                    if not model._mx_active else
-                                    "head_patch16_kernel<MX> (cf_head_fused mx: v_mfma_f32_16x16x32_f16 + v_mfma_scale_f32_16x16x128_f8f6f4 first layer, "
-                                    "v_mfma_f32_16x16x32_bf16 tail layers; 2 launches/step: 7 primary heads, 4 secondary heads)"),
-                         "note": ("algorithmic FLOPs (2*MACs) against the fp32 MFMA peak" if args.exact_fp32 else
-                                  "algorithmic FLOPs (2*MACs); the kernel issues 3 bf16 MFMA passes per MAC "
-                                  "(split operands), so MFMA-pipe utilisation is 3x frac" if not model._mx_active else
-                                  "algorithmic FLOPs (2*MACs) against the dense bf16/f16 MFMA peak; a first-layer MAC costs 1 fp16 pass + "
-                                  "1/2 pass-equivalent of FP6 cross terms (4x rate), a 1x1-layer MAC 3 bf16 passes"),
-                         "flop_per_launch": launch_flops, "avg_launch_ms": round(avg_ms, 4),
-                         "launches_timed": len(launch_ms)},
         }
+        if args.full:
+            avg_ms = float(np.mean(launch_ms))
+            launch_flops = launch_flops / len(launch_ms)          # algorithmic FLOPs of an average launch
+            achieved = launch_flops / (avg_ms * 1e-3) / 1e12
+            peak = FP32_MFMA_PEAK_TFLOPS if args.exact_fp32 else BF16_MFMA_PEAK_TFLOPS
+            result["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak,
+                                 "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                                 "traffic": None if args.exact_fp32 else measured_traffic(),
+                                 "kernel": ("conv_igemm_kernel (fp32 MFMA; the 3x3 first layers of the 7 primary / 4 secondary heads)"
+                                            if args.exact_fp32 else
+                                            "head_patch16_kernel (cf_head_fused, v_mfma_f32_16x16x32_bf16; 2 launches/step: 7 primary heads, 4 secondary heads)"
+                                            if not model._mx_active else
+                                            "head_patch16_kernel<MX> (cf_head_fused mx: v_mfma_f32_16x16x32_f16 + v_mfma_scale_f32_16x16x128_f8f6f4 first layer, "
+                                            "v_mfma_f32_16x16x32_bf16 tail layers; 2 launches/step: 7 primary heads, 4 secondary heads)"),
+                                 "note": ("algorithmic FLOPs (2*MACs) against the fp32 MFMA peak" if args.exact_fp32 else
+                                          "algorithmic FLOPs (2*MACs); the kernel issues 3 bf16 MFMA passes per MAC "
+                                          "(split operands), so MFMA-pipe utilisation is 3x frac" if not model._mx_active else
+                                          "algorithmic FLOPs (2*MACs) against the dense bf16/f16 MFMA peak; a first-layer MAC costs 1 fp16 pass + "
+                                          "1/2 pass-equivalent of FP6 cross terms (4x rate), a 1x1-layer MAC 3 bf16 passes"),
+                                 "flop_per_launch": launch_flops, "avg_launch_ms": round(avg_ms, 4),
+                                 "launches_timed": len(launch_ms)}
         if gather is not None:
             g_avg_ms, g_b, g_n = gather
             gbs = g_b / (g_avg_ms * 1e-3) / 1e9
@@ -840,14 +880,15 @@ def main():
                 "traffic": measured_traffic(prefixes=("dcn_f16x3_kernel<2, 2, 1, true, 1>",)),   # HBM-side bytes per launch (all 20 launches of the form)
                 "bytes_per_launch": g_b, "avg_launch_ms": round(g_avg_ms, 4), "launches_timed": g_n}
         default_run = (B, H, W) == (16, 448, 800) and not args.exact_fp32 and args.offset_std == 0.01
-        if not args.no_cpu_baseline and world == 1:
-            if default_run:
-                del images, pc_dep
-                torch.cuda.empty_cache()
-                result["other_configs"] = other_configs(dev)
-            result["cpu_baseline"] = cpu_baseline(H, W, batch=B)
-        elif world == 1:
-            result["cpu_baseline"] = None
+        if args.full and world == 1:
+            if args.no_cpu_baseline:
+                result["cpu_baseline"] = None
+            else:
+                if default_run:
+                    del images, pc_dep
+                    torch.cuda.empty_cache()
+                    result["other_configs"] = other_configs(dev)
+                result["cpu_baseline"] = cpu_baseline(H, W, batch=B)
         os.write(json_fd, (json.dumps(result) + "\n").encode())
     if collective:
         dist.destroy_process_group()

@@ -1,6 +1,7 @@
 """DEV-ONLY: legacy parameter names for every key of the CenterFusion / CenterNet state_dict, produced by
 the REFERENCE's own `toggleWeightName` (/root/reference/src/lib/model/model.py:169-250), and a check that the
-reference's `elasticLoadStateDict` loads a legacy-keyed checkpoint into OUR module unchanged.
+reference's `elasticLoadStateDict` loads a legacy-keyed checkpoint into OUR module unchanged (what it loaded where is
+recorded in the fixture, so the test suite checks it without the reference).
     python tests/golden/make_golden_legacy.py"""
 import os
 import sys
@@ -36,6 +37,20 @@ def main():
         m2 = elasticLoadStateDict(getModel(cfg), legacy)
         for k, v in m2.state_dict().items():
             assert torch.equal(v, src[k]), k
+        # recorded for tests/test_host_logic.py (which runs without the reference): the shapes of every key the
+        # reference's loader was given our module with, and for every key the checkpoint entry it loaded there
+        # ("" = the module kept its own tensor).  Every entry is made distinct - integer buffers too - so the source
+        # of each loaded tensor is unambiguous.
+        distinct = {k: (v if v.is_floating_point() else torch.full_like(v, 1000 + i)) for i, (k, v) in enumerate(src.items())}
+        ckpt = {"module." + o: distinct[k] for k, o in zip(keys, old)}
+        m3 = elasticLoadStateDict(getModel(cfg), ckpt)
+        loaded_from = []
+        for k, v in m3.state_dict().items():
+            hit = [ck for ck, cv in ckpt.items() if cv.shape == v.shape and torch.equal(cv, v)]
+            assert len(hit) <= 1, (k, hit)
+            loaded_from.append(hit[0] if hit else "")
+        out[f"{tag}_shapes"] = np.array([",".join(map(str, v.shape)) for v in m.state_dict().values()])
+        out[f"{tag}_refload_from"] = np.array(loaded_from)
         print(f"{tag}: {len(keys)} keys, {sum(a != k for a, k in zip(old, keys))} renamed (v1), "
               f"{sum(a != k for a, k in zip(old2, keys))} renamed (v2); reference elasticLoadStateDict -> our DLASeg ok")
     np.savez_compressed(os.path.join(HERE, "legacy_keys.npz"), **out)

@@ -284,7 +284,7 @@ def test_bench_line_carries_every_ranks_diagnostics(dev):
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-collective", "--steps", "4", "--warmup",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-collective", "--full", "--steps", "4", "--warmup",
                         "2", "--no-cpu-baseline", "--batch", "2", "--height", "128", "--width", "160"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -296,6 +296,33 @@ def test_bench_line_carries_every_ranks_diagnostics(dev):
     assert r["rank"] == 0 and 0 < r["host_enqueue_ms"] and 0 < r["step_ms"] == pytest.approx(d["ms_per_step"], rel=1e-3)
     assert 0 <= r["gather_wait_ms"] < r["step_ms"] and 0 <= r["gather_wait_host_ms"] < r["step_ms"]
     assert d["roofline"]["launches_timed"] == 8
+
+
+def test_bench_plain_line_and_dumped_outputs(dev, tmp_path):
+    """A plain bench.py run prints the headline line and nothing that needs runs of its own (that is --full's); with
+    --dump-outputs it writes the last timed step's postProcess rows, and two runs with equal arguments write equal files."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    posts = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--batch", "2", "--height", "128", "--width", "160", "--dump-outputs", str(out)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, p.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+        assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(2 * 1e3 / d["ms_per_step"], rel=2e-3)
+        assert isinstance(d["dtype"], str) and d["dtype"]
+        assert not {"roofline", "roofline_gather", "other_configs", "cpu_baseline"} & set(d)
+        assert sorted(os.listdir(out)) == ["post.npy"]
+        post = np.load(out / "post.npy")
+        assert post.dtype == np.float32 and post.shape == (2, 100, 54) and np.isfinite(post).all()
+        posts.append(post)
+    assert np.array_equal(posts[0], posts[1])
 
 
 def test_stream_probe_tells_shared_queue_from_concurrent(dev):

@@ -230,30 +230,26 @@ def test_detector_constructor_is_the_references(tmp_path):
 
 
 def test_reference_loader_accepts_our_module():
-    """Where the reference is present (the build container): its own elasticLoadStateDict drives OUR module."""
-    import os, sys
-    if not os.path.isdir("/root/reference/src/lib"):
-        pytest.skip("reference tree not present on this machine")
-    from tests.golden import make_golden
-    saved_path, saved_mods = list(sys.path), dict(sys.modules)
-    try:
-        make_golden._install_inert_modules()
-        sys.path[:0] = ["/root/reference/src", "/root/reference/src/lib"]
-        from model.model import elasticLoadStateDict, toggleWeightName
-        cfg = centerfusion_middle_config((64, 64))
+    """The reference's own elasticLoadStateDict, given OUR module and a DataParallel checkpoint under the legacy names,
+    loaded every entry into the key of the same name and shape (tests/golden/legacy_keys.npz records, per key, the shape
+    it saw and the checkpoint entry it loaded there; make_golden_legacy.py).  Our module still has those keys and
+    shapes, and our loader puts every entry where the reference's did."""
+    from centerfusiondetect3d_amd import checkpoint as ck
+    g = _legacy_fixture()
+    for tag, cfg in (("centerfusion", centerfusion_middle_config), ("centernet", centernet_config)):
+        new, old = list(g[f"{tag}_new"]), list(g[f"{tag}_old"])
+        shapes, loaded_from = list(g[f"{tag}_shapes"]), list(g[f"{tag}_refload_from"])
+        assert len(shapes) == len(loaded_from) == len(new)
+        assert loaded_from == ["module." + o for o in old]              # the reference kept none of the module's own tensors
+        own = getModel(cfg((64, 64))).state_dict()
+        assert list(own) == new and [",".join(map(str, v.shape)) for v in own.values()] == shapes
         gen = torch.Generator().manual_seed(4)
-        src = {k: (torch.randn(v.shape, generator=gen) if v.is_floating_point() else v.clone())
-               for k, v in getModel(cfg).state_dict().items()}
-        legacy = {toggleWeightName(k, "old"): v for k, v in src.items()}
-        m = elasticLoadStateDict(getModel(cfg), legacy)
-        for k, v in m.state_dict().items():
-            assert torch.equal(v, src[k]), k
-    finally:
-        sys.path[:] = saved_path
-        for k in list(sys.modules):
-            if k not in saved_mods:
-                del sys.modules[k]
-        sys.modules.update(saved_mods)
+        ckpt = {"module." + o: (torch.randn(own[k].shape, generator=gen) if own[k].is_floating_point()
+                                else torch.full_like(own[k], 1000 + i)) for i, (k, o) in enumerate(zip(new, old))}
+        m, rep = ck.elastic_load_state_dict(getModel(cfg((64, 64))), ckpt)
+        assert not rep["dropped"] and not rep["skipped_shape"] and not rep["missing"]
+        for (k, v), src in zip(m.state_dict().items(), loaded_from):
+            assert torch.equal(v, ckpt[src]), (tag, k, src)
 
 
 def test_no_exec_masked_prefetch_in_pinned_loops():

@@ -8,8 +8,8 @@ TAG=${1:-r4}
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-C2="bench.py --steps 5 --warmup 2 --no-cpu-baseline"
-C5="bench.py --steps 5 --warmup 2 --no-cpu-baseline --batch 8 --height 896 --width 1600"
+C2="bench.py --full --steps 5 --warmup 2 --no-cpu-baseline"
+C5="bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --batch 8 --height 896 --width 1600"
 SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA"
 for cfg in c2 c5; do
   if [ $cfg = c2 ]; then ARGS=$C2; else ARGS=$C5; fi
