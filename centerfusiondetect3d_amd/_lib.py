@@ -131,6 +131,8 @@ SYMBOLS = {
     "cf_checksum64": (_i, [_f, C.c_long, _f, _f]),
     "cf_frustum_assoc": (_i, [_f, _i, _f, _f, _f, _f, _f, _f, _i, _i, _i, C.c_float, _f, _f, _f, _f]),
     "cf_topk_frustum": (_i, [_f, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _i, C.c_float, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "cf_pc_hm_direct": (_i, [_f, _i, _i, _i, C.c_float, _f, _f, _f]),
+    "cf_radar_roi_expand": (_i, [_f, _f, _f, _i, _i, _i, _f, _f, _i, _i, _i, _f, _f, _f, _f]),
     "cf_pillar_expand": (_i, [_f, _f, _f, _i, _i, _i, _f, _f, _i, _i, _d, _d, _d, _f, _f, _f, _f]),
     "cf_decode_gather": (_i, [C.POINTER(DecodeArgs), _f]),
     "cf_post_process": (_i, [_f, _f, _f, _i, _i, _i, _i, _f, _f]),

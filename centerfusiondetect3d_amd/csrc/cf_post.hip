@@ -796,6 +796,65 @@ __global__ __launch_bounds__(FR_THREADS) void frustum_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
+// Middle fusion WITHOUT frustum association (base_model.py:69-79): the radar map itself is the secondary heads' pc_hm.
+// One pass: channel 0 of pc_dep is normalised IN PLACE, x -> 1 - x / max_pc_dist (a true fp32 division, then the
+// subtraction: the bits of torch's `x /= d; x = 1 - x` on the CPU), and the three channels are written channels-last in the
+// two forms the secondary head launch reads - exactly what frustum_kernel writes.  V pixels per thread (V = 4: one
+// 16-byte load per channel plane, 16-byte stores; V = 1 for maps / pointers that are not 16-byte aligned).
+// ---------------------------------------------------------------------------------------------
+constexpr int PD_THREADS = 256;
+
+template <int V>
+__global__ __launch_bounds__(PD_THREADS) void pc_hm_direct_kernel(float* __restrict__ pc_dep, long n_groups, int HW,
+                                                                  float max_pc_dist, f32x4* __restrict__ pc_hm_nhwc4,
+                                                                  u32x4p* __restrict__ pc_hm_split8) {
+  const long g = (long)blockIdx.x * PD_THREADS + threadIdx.x;
+  if (g >= n_groups) return;
+  const long pix = g * V;                       // first pixel of the group, over B * HW (V divides HW: one image per group)
+  const long b = pix / HW;
+  float* p0 = pc_dep + b * 3 * (long)HW + (pix - b * HW);
+  float v0[V], v1[V], v2[V];
+  if constexpr (V == 4) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(p0);
+    const f32x4 c = *reinterpret_cast<const f32x4*>(p0 + HW);
+    const f32x4 d = *reinterpret_cast<const f32x4*>(p0 + 2 * (long)HW);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { v0[i] = a[i]; v1[i] = c[i]; v2[i] = d[i]; }
+  } else {
+    v0[0] = p0[0]; v1[0] = p0[HW]; v2[0] = p0[2 * (long)HW];
+  }
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    const float q = v0[i] / max_pc_dist;
+    v0[i] = 1.0f - q;
+  }
+  if constexpr (V == 4) {
+    const f32x4 o = {v0[0], v0[1], v0[2], v0[3]};
+    *reinterpret_cast<f32x4*>(p0) = o;
+  } else {
+    p0[0] = v0[0];
+  }
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    if (pc_hm_nhwc4) {
+      const f32x4 o = {v0[i], v1[i], v2[i], 0.0f};
+      pc_hm_nhwc4[pix + i] = o;
+    }
+    if (pc_hm_split8) {  // [pixel][hi 8][lo 8] bf16, channels 3..7 zero
+      const float h0 = (float)(__bf16)v0[i], h1 = (float)(__bf16)v1[i], h2 = (float)(__bf16)v2[i];
+      auto pk = [](float lo16, float hi16) {
+        return ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)hi16) << 16) |
+               __builtin_bit_cast(unsigned short, (__bf16)lo16);
+      };
+      const u32x4p hi = {pk(h0, h1), pk(h2, 0.0f), 0u, 0u};
+      const u32x4p lo = {pk(v0[i] - h0, v1[i] - h1), pk(v2[i] - h2, 0.0f), 0u, 0u};
+      pc_hm_split8[(pix + i) * 2] = hi;
+      pc_hm_split8[(pix + i) * 2 + 1] = lo;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Detection gather (model/decode.py:40-41, 60-64, 132-172)
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void decode_row(const cf_decode_args& a, int t, float* o) {
@@ -1090,6 +1149,32 @@ struct PlBox {
 // point atomicMax-es its depth rank over its rectangle, a wave per point (points are depth-ascending,
 // painting order = rank order, so the surviving value of a pixel is that of its highest rank);
 // (3) resolve ranks to (depth, vx, vz).  The rank map is processed in row bands that fit LDS.
+// METHOD (DATASET.PC_ROI_METHOD, generic_dataset.py:774-826): 0 = "pillars", 1 = "points" (drawPcPoints, nuscenes.py:265-294: the one
+// pixel the truncated coordinates name; of several points on a pixel the last in order stays, as the rank map has it),
+// 2 = "heatmap" (a square of the Gaussian radius of a (250 / depth + 5)-sized object around the truncated centre).
+constexpr int ROI_PILLARS = 0, ROI_POINTS = 1, ROI_HEATMAP = 2;
+
+// utils/image.py:145-176 (getGaussianRadius((r, r), min_overlap = 0.7)) in float64, operation by operation
+__device__ __forceinline__ double gaussian_radius_sq(double r) {
+  const double mo = 0.7;
+  const double height = r, width = r;
+  const double b1 = height + width;
+  const double c1 = width * height * (1 - mo) / (1 + mo);
+  const double sq1 = sqrt(b1 * b1 - 4 * 1 * c1);
+  const double r1 = (b1 + sq1) / 2;
+  const double b2 = 2 * (height + width);
+  const double c2 = (1 - mo) * width * height;
+  const double sq2 = sqrt(b2 * b2 - 4 * 4 * c2);
+  const double r2 = (b2 + sq2) / 2;
+  const double a3 = 4 * mo;
+  const double b3 = -2 * mo * (height + width);
+  const double c3 = (mo - 1) * width * height;
+  const double sq3 = sqrt(b3 * b3 - 4 * a3 * c3);
+  const double r3 = (b3 + sq3) / 2;
+  return fmin(fmin(r1, r2), r3);
+}
+
+template <int METHOD>
 __global__ __launch_bounds__(PL_THREADS) void pillar_kernel(
     const double* __restrict__ pc_2d, const double* __restrict__ pc_3d, const int32_t* __restrict__ counts,
     int max_n, int n_rows, const double* __restrict__ calib, const double* __restrict__ trans, int H, int W,
@@ -1115,7 +1200,27 @@ __global__ __launch_bounds__(PL_THREADS) void pillar_kernel(
       tx = m[0] * u + m[1] * v + m[2];
       ty = m[3] * u + m[4] * v + m[5];
       keep = (tx < (double)W) && (ty < (double)H) && (0.0 < tx) && (0.0 < ty);
-      if (keep) {
+      if (keep && METHOD == ROI_POINTS) {
+        const int x = (int)tx, y = (int)ty;              // astype(np.int32): truncation (0 < tx < W, 0 < ty < H)
+        py_slice(y, y + 1, H, bx.y0, bx.y1);
+        py_slice(x, x + 1, W, bx.x0, bx.x1);
+      } else if (keep && METHOD == ROI_HEATMAP) {
+        const double depth = p2[2 * (size_t)max_n + i];
+        double rad = gaussian_radius_sq((1.0 / depth) * 250 + 5);
+        if (!(rad < 1048576.0)) rad = 1048576.0;         // (depth -> 0: far beyond any map; the min() below clip it)
+        const int radius = max(0, (int)rad);
+        const int x = (int)tx, y = (int)ty;
+        const int left = min(x, radius), right = min(W - x, radius + 1);
+        const int top = min(y, radius), bottom = min(H - y, radius + 1);
+        py_slice(y - top, y + bottom, H, bx.y0, bx.y1);
+        py_slice(x - left, x + right, W, bx.x0, bx.x1);
+      }
+      if (keep && METHOD != ROI_PILLARS) {
+        bx.d = (float)p2[2 * (size_t)max_n + i];
+        bx.vx = (float)p3[8 * (size_t)max_n + i];
+        bx.vz = (float)p3[9 * (size_t)max_n + i];
+      }
+      if (keep && METHOD == ROI_PILLARS) {
         // 8 corners of the (h,w,l) pillar standing on the point, yaw 0; corner offsets are float32
         // in the reference (numpy float32 arrays), the sum with the fp64 location is fp64.
         const double X = p3[i], Y = p3[max_n + i], Z = p3[2 * (size_t)max_n + i];
@@ -1462,6 +1567,29 @@ extern "C" int cf_topk_frustum(const float* heat, int C, int K, const float* dep
   return cf_check_launch("cf_topk_frustum");
 }
 
+// Middle fusion without frustum association: normalise channel 0 of pc_dep in place and write the channels-last copies
+// the secondary head launch reads (pc_hm_direct_kernel above).
+extern "C" int cf_pc_hm_direct(float* pc_dep, int B, int H, int W, float max_pc_dist, float* pc_hm_nhwc4,
+                               void* pc_hm_split8, void* stream) {
+  CF_REQUIRE(pc_dep, "cf_pc_hm_direct: null pc_dep");
+  CF_REQUIRE(B > 0 && H > 0 && W > 0, "cf_pc_hm_direct: bad geometry (B=%d, H=%d, W=%d)", B, H, W);
+  CF_REQUIRE((long)B * H * W < (1L << 31) / 3, "cf_pc_hm_direct: map of %ld pixels", (long)B * H * W);
+  CF_REQUIRE(max_pc_dist > 0.0f, "cf_pc_hm_direct: max_pc_dist=%g must be positive", (double)max_pc_dist);
+  CF_REQUIRE(((uintptr_t)pc_hm_nhwc4 & 15) == 0 && ((uintptr_t)pc_hm_split8 & 15) == 0,
+             "cf_pc_hm_direct: pc_hm_nhwc4 / pc_hm_split8 must be 16-byte aligned");
+  const int HW = H * W;
+  const bool vec = (HW % 4 == 0) && (((uintptr_t)pc_dep & 15) == 0);
+  const long n_groups = (long)B * HW / (vec ? 4 : 1);
+  const unsigned blocks = (unsigned)((n_groups + PD_THREADS - 1) / PD_THREADS);
+  if (vec)
+    hipLaunchKernelGGL(pc_hm_direct_kernel<4>, dim3(blocks), dim3(PD_THREADS), 0, (hipStream_t)stream, pc_dep, n_groups, HW,
+                       max_pc_dist, reinterpret_cast<f32x4*>(pc_hm_nhwc4), static_cast<u32x4p*>(pc_hm_split8));
+  else
+    hipLaunchKernelGGL(pc_hm_direct_kernel<1>, dim3(blocks), dim3(PD_THREADS), 0, (hipStream_t)stream, pc_dep, n_groups, HW,
+                       max_pc_dist, reinterpret_cast<f32x4*>(pc_hm_nhwc4), static_cast<u32x4p*>(pc_hm_split8));
+  return cf_check_launch("cf_pc_hm_direct");
+}
+
 extern "C" int cf_decode_gather(const cf_decode_args* a, void* stream) {
   CF_REQUIRE(a && a->scores && a->inds && a->classes && a->det, "cf_decode_gather: null buffer");
   CF_REQUIRE(a->B > 0 && a->K > 0 && a->H > 0 && a->W > 0, "cf_decode_gather: bad geometry");
@@ -1523,11 +1651,41 @@ extern "C" int cf_pillar_expand(const double* pc_2d, const double* pc_3d, const 
   CF_REQUIRE(band_rows >= 1, "cf_pillar_expand: W=%d too wide", W);
   const size_t lds = (size_t)band_rows * W * sizeof(int);
   static CfLdsLimit lds_limit;
-  lds_limit.ensure(pillar_kernel, lds, 65536);
-  hipLaunchKernelGGL(pillar_kernel, dim3(B), dim3(PL_THREADS), lds, (hipStream_t)stream, pc_2d, pc_3d, counts,
+  lds_limit.ensure(pillar_kernel<ROI_PILLARS>, lds, 65536);
+  hipLaunchKernelGGL(pillar_kernel<ROI_PILLARS>, dim3(B), dim3(PL_THREADS), lds, (hipStream_t)stream, pc_2d, pc_3d, counts,
                      max_n, n_rows, calib, trans, H, W, pillar_h, pillar_w, pillar_l, pc_dep, keep_mask, xy_out,
                      band_rows);
   return cf_check_launch("cf_pillar_expand");
+}
+
+// DATASET.PC_ROI_METHOD "points" / "heatmap" (method 1 / 2; 0 = pillars with the reference's default pillar): the inputs and
+// outputs of cf_pillar_expand, the same rank-map painting.
+extern "C" int cf_radar_roi_expand(const double* pc_2d, const double* pc_3d, const int32_t* counts, int B, int max_n,
+                                   int n_rows, const double* calib, const double* trans, int H, int W, int method,
+                                   float* pc_dep, uint8_t* keep_mask, double* xy_out, void* stream) {
+  CF_REQUIRE(pc_2d && pc_3d && counts && calib && trans && pc_dep, "cf_radar_roi_expand: null buffer");
+  CF_REQUIRE(B > 0 && H > 0 && W > 0, "cf_radar_roi_expand: bad geometry");
+  CF_REQUIRE(max_n >= 1 && max_n <= PL_MAXN, "cf_radar_roi_expand: max_n=%d outside [1,%d]", max_n, PL_MAXN);
+  CF_REQUIRE(n_rows >= 10, "cf_radar_roi_expand: pc_3d needs >= 10 rows (8 = vx, 9 = vz)");
+  CF_REQUIRE(method == ROI_POINTS || method == ROI_HEATMAP,
+             "cf_radar_roi_expand: method=%d (1 = points, 2 = heatmap; pillars: cf_pillar_expand)", method);
+  int band_rows = H;
+  const int max_cells = (96 * 1024) / 4;  // 96 KiB of rank map per workgroup
+  if ((long)band_rows * W > max_cells) band_rows = max_cells / W;
+  CF_REQUIRE(band_rows >= 1, "cf_radar_roi_expand: W=%d too wide", W);
+  const size_t lds = (size_t)band_rows * W * sizeof(int);
+  if (method == ROI_POINTS) {
+    static CfLdsLimit lim;
+    lim.ensure(pillar_kernel<ROI_POINTS>, lds, 65536);
+    hipLaunchKernelGGL(pillar_kernel<ROI_POINTS>, dim3(B), dim3(PL_THREADS), lds, (hipStream_t)stream, pc_2d, pc_3d, counts,
+                       max_n, n_rows, calib, trans, H, W, 0.0, 0.0, 0.0, pc_dep, keep_mask, xy_out, band_rows);
+  } else {
+    static CfLdsLimit lim;
+    lim.ensure(pillar_kernel<ROI_HEATMAP>, lds, 65536);
+    hipLaunchKernelGGL(pillar_kernel<ROI_HEATMAP>, dim3(B), dim3(PL_THREADS), lds, (hipStream_t)stream, pc_2d, pc_3d, counts,
+                       max_n, n_rows, calib, trans, H, W, 0.0, 0.0, 0.0, pc_dep, keep_mask, xy_out, band_rows);
+  }
+  return cf_check_launch("cf_radar_roi_expand");
 }
 
 extern "C" int cf_preprocess_images(const uint8_t* src, int B, int Hs, int Ws, const double* map_dst_to_src,

@@ -3,7 +3,7 @@ path, end to end on the device:
 
     uint8 camera frames + raw radar sweeps
       -> preProcessImages        (cf_preprocess_images:   detector.py:206-234)
-      -> radar_to_pc_dep         (cf_radar_ingest + cf_pillar_expand:  detector.py:257-292)
+      -> radar_to_pc_dep         (cf_radar_ingest + cf_pillar_expand | cf_radar_roi_expand, by DATASET.PC_ROI_METHOD:  detector.py:257-292)
       -> model(images, pc_dep=, calib=)                   (detector.py:423)
       -> fusionDecode + postProcess in one gather launch  (cf_decode_post: detector.py:343-349, 397-426)
       -> merge_outputs                                    (detector.py:428-470)
@@ -108,7 +108,8 @@ class Detector(object):
                                                                           for i in img_infos]),
                                       transMatOutput, (outH, outW), max_dist=float(self.config.DATASET.MAX_PC_DIST),
                                       z_offset=float(self.config.DATASET.PC_Z_OFFSET),
-                                      pillar_dims=tuple(self.config.DATASET.PILLAR_DIMS), device=self.device)
+                                      pillar_dims=tuple(self.config.DATASET.PILLAR_DIMS), device=self.device,
+                                      roi_method=getattr(self.config.DATASET, "PC_ROI_METHOD", "pillars"))
         calibs = torch.from_numpy(np.stack(calibs, axis=0)).to(self.device)
         return images, pc_deps, metas, calibs
 

@@ -273,6 +273,7 @@ class _Plan:
         cfg = model.config
         heads, head_conv = dict(cfg.heads), {k: list(v) for k, v in cfg.head_conv.items()}
         radar = model.isRadarEnabled and model.fusionStrategy == "middle"
+        frustum = radar and model.isFrustumEnabled     # False on a radar model: the radar map itself is pc_hm (base_model.py:69-79)
         K = int(cfg.MODEL.K)
 
         def buf(*shape, dtype=torch.float32):
@@ -608,26 +609,34 @@ class _Plan:
             fused_heads("tails.primary", primary, [feat_in], [64])
             # radar: the lane starts behind the frustum chain (below), not behind the primary launch - its chip-wide NMS pass
             # beside the chain's slice top-k tripled that kernel's time (41 vs 14 us) on the one path everything waits for
-            if not (radar and model.peaks_behind_frustum):
+            # (no frustum chain - MODEL.FRUSTUM = False -: behind the primary launch, as on a camera-only model)
+            if not (frustum and model.peaks_behind_frustum):
                 peaks_lane()
         elif fuse_all:
             fused_heads("tails.primary", primary, [feat_in], [64])
         else:
             for h in primary:
                 head_out(h, hid, hs)
+        self.frustum = frustum
         if radar:
             self.pc_hm4 = None if bf else buf(B, h4, w4, 4)
             self.pc_hm8 = buf(B, h4, w4, 2, 8, dtype=torch.bfloat16) if bf else None
-            self.tk_scores = buf(B, K)
-            self.tk_inds = buf(B, K, dtype=torch.int32)
-            self.tk_cls = buf(B, K, dtype=torch.int32)
-            self.tk_ws = buf(max(1, self.lib.cf_topk_workspace_bytes(B, K)), dtype=torch.uint8)
-            # top-k of the raw heat map -> association (pointcloud.py:347-392): cf_topk_frustum (two launches: the merge of the slice
-            # lists runs in the association kernel's prologue) or, model.frustum_fused = False, cf_topk_peaks + cf_frustum_assoc (three)
             self.topk_step = None
-            if not model.frustum_fused:
-                self.topk_step = len(self.steps); self.add_step(None)
+            if frustum:
+                self.tk_scores = buf(B, K)
+                self.tk_inds = buf(B, K, dtype=torch.int32)
+                self.tk_cls = buf(B, K, dtype=torch.int32)
+                self.tk_ws = buf(max(1, self.lib.cf_topk_workspace_bytes(B, K)), dtype=torch.uint8)
+                # top-k of the raw heat map -> association (pointcloud.py:347-392): cf_topk_frustum (two launches: the merge of the slice
+                # lists runs in the association kernel's prologue) or, model.frustum_fused = False, cf_topk_peaks + cf_frustum_assoc (three)
+                if not model.frustum_fused:
+                    self.topk_step = len(self.steps); self.add_step(None)
+            # (MODEL.FRUSTUM = False: no top-k, no association - the slot holds cf_pc_hm_direct, which normalises the caller's map in
+            #  place and writes the secondary heads' channels-last copies; the secondary launch then depends on nothing the primary wrote)
             self.frustum_step = len(self.steps); self.add_step(None)
+            if not frustum:
+                self.step_index["pc_hm_direct"] = self.frustum_step
+                self.step_flops["pc_hm_direct"] = 0.0
             ss = 256 * len(SECONDARY_HEADS)
             if split and self.peaks_step is None:
                 peaks_lane()
@@ -767,7 +776,23 @@ class _Plan:
                 self.steps[self.in_step] = (lib.cf_stem_fused, C.byref(self.stem))
             else:
                 self.steps[self.in_step] = (lib.cf_nchw_to_nhwc4, x.data_ptr(), self.x4.data_ptr(), B, 3, H, W)
-        if self.radar:
+        if self.radar and not self.frustum:
+            # base_model.py:69-79 + detectHeads.py:172-190: ONE in-place normalisation of the caller's tensor per forward; pc_hm_in,
+            # pc_hm and pc_hm_out are all channel 0 of that tensor
+            self.steps[self.frustum_step] = (
+                lib.cf_pc_hm_direct, pc_dep.data_ptr(), B, h4, w4, C.c_float(float(model.config.DATASET.MAX_PC_DIST)),
+                _lib.ptr(self.pc_hm4), _lib.ptr(self.pc_hm8))
+            y["pc_hm_in"] = pc_dep[:, :1]
+            y["pc_hm"] = pc_dep[:, 0, :, :].unsqueeze(1)
+            for h in SECONDARY_HEADS:
+                t = new(heads[h])
+                y[h] = t
+                set_out(h, t)
+            y["pc_hm_out"] = pc_dep[:, :1]
+            y["depthMap"] = y["depth2"]                    # raw depth2 logits (detectHeads.py:188-190)
+            y["depth2"] = new(1)
+            set_out("depth2", y["depth2"], second=True)
+        elif self.radar:
             pc_hm = new(3)
             if self.topk_step is None:
                 self.steps[self.frustum_step] = (
@@ -840,8 +865,8 @@ class DLASeg(nn.Module):
         self.fusionStrategy = config.MODEL.FUSION_STRATEGY if self.isRadarEnabled else None
         if self.fusionStrategy not in (None, "middle"):
             raise NotImplementedError(f"fusion strategy {self.fusionStrategy!r} is outside the hot path")
-        if self.isRadarEnabled and not config.MODEL.FRUSTUM:
-            raise NotImplementedError("middle fusion without frustum association is outside the hot path")
+        # middle fusion with MODEL.FRUSTUM = False: the normalised radar map goes straight to the secondary heads (base_model.py:69-79)
+        self.isFrustumEnabled = self.isRadarEnabled and bool(config.MODEL.FRUSTUM)
         try:                                               # dla.py:578-580
             config.defrost()
             config.MODEL.PYRAMID_OUT_SIZE = [config.MODEL.OUTPUT_SIZE]
@@ -1180,6 +1205,8 @@ class DLASeg(nn.Module):
             shadow.load_state_dict(self.state_dict())
             shadow.to(images.device)
             shadow.conv_f16, shadow.heads_bf16, shadow.streams, shadow.lanes, shadow.use_graph = False, False, 1, False, False
+            if pc_dep is not None and self.isRadarEnabled and not self.isFrustumEnabled:
+                pc_dep = pc_dep.clone()        # (without frustum the forward normalises pc_dep in place: that one mutation is the real forward's)
             shadow(images, pc_dep=pc_dep, calib=calib)
             r = shadow.activation_ranges()
             del shadow
@@ -1304,13 +1331,17 @@ class DLASeg(nn.Module):
         the heads - captured ONCE as a HIP graph over static input / output buffers and replayed per call (one
         hipGraphLaunch instead of ~100-350 launches from Python: with 4 trunk streams the eager path is bound by the
         host's launch rate).  Semantics are those of the eager forward: fresh output tensors every call (copies out
-        of the static ones), `pc_hm_in` a view of the CALLER's pc_dep, `calib` the caller's tensor."""
+        of the static ones), `pc_hm_in` a view of the CALLER's pc_dep, `calib` the caller's tensor.  MODEL.FRUSTUM = False:
+        the graph normalises its static copy of pc_dep; channel 0 is copied back, so the caller's tensor ends up normalised
+        exactly once per call and `pc_hm_in` / `pc_hm` / `pc_hm_out` are views of it, as in the eager forward."""
+        in_place = pc_dep is not None and self.isRadarEnabled and not self.isFrustumEnabled
         key = (B, H, W, dev, sid, "graph", self.streams)
         g = self._graphs.pop(key, None)
         if g is None:
             # warm-up (one-time attribute calls, the stream probe) with a throw-away plan set: its buffers are freed
             # again before the capture allocates the set the graph keeps
-            self._forward_eager(x, pc_dep, calib, B, H, W, dev, sid, store={})
+            # (in_place: the warm-up must not be the caller's tensor's first normalisation)
+            self._forward_eager(x, pc_dep.clone() if in_place else pc_dep, calib, B, H, W, dev, sid, store={})
             torch.cuda.synchronize(dev)
             gx = x.clone()
             gpc = pc_dep.clone() if pc_dep is not None else None
@@ -1345,12 +1376,16 @@ class DLASeg(nn.Module):
         if gcal is not None:
             gcal.copy_(calib)
         graph.replay()
+        if in_place:
+            pc_dep[:, :1].copy_(gpc[:, :1])
         y, fresh = {}, {}
         for k, v in gout.items():
             if k == "calib":
                 y[k] = calib
-            elif k == "pc_hm_in":
+            elif k == "pc_hm_in" or (in_place and k == "pc_hm_out"):
                 y[k] = pc_dep[:, :1]
+            elif in_place and k == "pc_hm":
+                y[k] = pc_dep[:, 0, :, :].unsqueeze(1)
             else:                                                   # aliases in gout stay aliases (depthMap / pc_hm views)
                 base = v._base if v._base is not None else v
                 if id(base) not in fresh:

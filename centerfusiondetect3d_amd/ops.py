@@ -714,6 +714,40 @@ def pillar_expand(pc_2d, pc_3d, counts, calib, trans, out_hw, pillar_dims=(1.5, 
     return (pc_dep, keep, xy) if want_aux else pc_dep
 
 
+ROI_METHODS = {"pillars": 0, "points": 1, "heatmap": 2}     # DATASET.PC_ROI_METHOD -> `method` of cf_radar_roi_expand
+
+
+def roi_method_id(roi_method):
+    """generic_dataset.py:820-821: anything but the three known methods raises (before any device work)."""
+    if roi_method not in ROI_METHODS:
+        raise ValueError(f"Invalid PC_ROI_METHOD: {roi_method}")
+    return ROI_METHODS[roi_method]
+
+
+def radar_roi_expand(pc_2d, pc_3d, counts, calib, trans, out_hw, roi_method, want_aux=False):
+    """cf_radar_roi_expand: the inputs / outputs of `pillar_expand` for roi_method "points" (one pixel per point) or "heatmap"
+    (a depth-dependent square per point)."""
+    method = roi_method_id(roi_method)
+    if method == 0:
+        raise ValueError("radar_roi_expand: 'pillars' is pillar_expand (it needs the pillar dimensions)")
+    _need_cuda(pc_2d, pc_3d, counts, calib, trans)
+    B, _, max_n = pc_2d.shape
+    H, W = out_hw
+    dev = pc_2d.device
+    pc_dep = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32)
+    keep = torch.empty((B, max_n), device=dev, dtype=torch.uint8) if want_aux else None
+    xy = torch.empty((B, 2, max_n), device=dev, dtype=torch.float64) if want_aux else None
+    for t, dt in ((pc_2d, torch.float64), (pc_3d, torch.float64), (counts, torch.int32),
+                  (calib, torch.float64), (trans, torch.float64)):
+        if t.dtype != dt or not t.is_contiguous():
+            raise _lib.CfHipError("cf_radar_roi_expand: wrong dtype / non-contiguous input")
+    _lib.check(_lib.load().cf_radar_roi_expand(pc_2d.data_ptr(), pc_3d.data_ptr(), counts.data_ptr(),
+                                               B, max_n, pc_3d.shape[1], calib.data_ptr(), trans.data_ptr(), H, W, method,
+                                               pc_dep.data_ptr(), _lib.ptr(keep), _lib.ptr(xy),
+                                               _lib.stream_ptr()), "cf_radar_roi_expand")
+    return (pc_dep, keep, xy) if want_aux else pc_dep
+
+
 def stem_args(ps, x, out, shape=None, out_pool=None, in_scales=None) -> _lib.StemArgs:
     """x may be None with shape=(B, C, H, W) given: the image pointer is then patched in per call.
     out_pool: optional (B, H/4, W/4, 32) buffer for the 2x2 max-pool of the level1 map.

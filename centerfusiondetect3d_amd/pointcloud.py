@@ -1,7 +1,7 @@
 """Drop-ins for the radar steps of the hot path, HIP-backed.
 
   getPcFrustumHeatmap(output, pc_dep, calib, config)  <- utils/pointcloud.py:331-394
-  process_point_cloud_batch(...)                       <- dataset/generic_dataset.py:738-828
+  process_point_cloud_batch(...)                       <- dataset/generic_dataset.py:738-828 (all three PC_ROI_METHODs)
   getAffineTransform(center, scale, 0, out_wh)         <- utils/image.py:43-83 (host, 3-point solve)
 """
 import numpy as np
@@ -39,11 +39,18 @@ def getAffineTransform(center, scale, rotateFactor, outputSize):
     return np.linalg.solve(A, dst.astype(np.float64)).T.copy()
 
 
+def _expand(pc_2d, pc_3d, counts, calibs, trans, out_hw, pillar_dims, roi_method):
+    if roi_method == "pillars":
+        return ops.pillar_expand(pc_2d, pc_3d, counts, calibs, trans, out_hw, pillar_dims)
+    return ops.radar_roi_expand(pc_2d, pc_3d, counts, calibs, trans, out_hw, roi_method)
+
+
 def process_point_cloud_batch(pc_2d_list, pc_3d_list, calibs, trans_out, out_hw, pillar_dims=(1.5, 0.2, 0.2),
-                              device="cuda", max_points=1024):
-    """Batched processPointCloud (PC_ROI_METHOD='pillars'): per-frame (3,N) / (R,N) float64 arrays
-    (already <= MAX_PC_DIST-filtered, image-projected and depth-sorted ascending, as
+                              device="cuda", max_points=1024, roi_method="pillars"):
+    """Batched processPointCloud (DATASET.PC_ROI_METHOD = `roi_method`: "pillars", "points" or "heatmap"): per-frame
+    (3,N) / (R,N) float64 arrays (already <= MAX_PC_DIST-filtered, image-projected and depth-sorted ascending, as
     detector.py:262-283 leaves them) -> pc_dep (B,3,H,W) float32 on `device`."""
+    ops.roi_method_id(roi_method)
     B = len(pc_2d_list)
     n_rows = max(10, max(p.shape[0] for p in pc_3d_list))
     max_n = max(1, max(p.shape[1] for p in pc_2d_list))
@@ -56,16 +63,20 @@ def process_point_cloud_batch(pc_2d_list, pc_3d_list, calibs, trans_out, out_hw,
     calibs = np.asarray(calibs, np.float64).reshape(B, 3, 4)
     trans = np.broadcast_to(np.asarray(trans_out, np.float64), (B, 2, 3)).copy()
     t = lambda a: torch.from_numpy(np.array(a, copy=True, order="C")).to(device)        # (a private, writable copy: torch refuses read-only arrays with a warning)
-    return ops.pillar_expand(t(p2), t(p3), t(cnt), t(calibs), t(trans), out_hw, pillar_dims)
+    return _expand(t(p2), t(p3), t(cnt), t(calibs), t(trans), out_hw, pillar_dims, roi_method)
 
 
 def radar_to_pc_dep(radar_pcs, intrinsics, img_wh, calibs, trans_out, out_hw, max_dist=60.0, z_offset=0.0,
-                    pillar_dims=(1.5, 0.2, 0.2), descending=False, device="cuda", max_points=1024):
+                    pillar_dims=(1.5, 0.2, 0.2), descending=False, device="cuda", max_points=1024, roi_method="pillars"):
     """Whole radar side of `Detector.pre_process` on the device (detector.py:257-292): raw per-frame
     sweeps (R x N float64 arrays as unpickled from annotations/radar_pc/<sensor>/<token>.bin, rows
     0..2 = x, y, z in the camera frame) -> depth gate, z offset, image projection + border gate, depth
     sort (cf_radar_ingest) -> pillar expansion (cf_pillar_expand) -> pc_dep (B,3,H,W) fp32.  Only the raw
-    points cross PCIe; nothing is filtered, projected or sorted on the host."""
+    points cross PCIe; nothing is filtered, projected or sorted on the host.
+    roi_method = DATASET.PC_ROI_METHOD (generic_dataset.py:774-826): "pillars", or "points" / "heatmap" (cf_radar_roi_expand);
+    anything else raises ValueError before the device is touched.  The sort is the detector's for every method (ascending:
+    detector.py:280-283 does not look at PC_REVERSE, which only the dataset loader reads)."""
+    ops.roi_method_id(roi_method)
     B = len(radar_pcs)
     arrs = [np.asarray(p, np.float64) for p in radar_pcs]
     n_rows = max(10, max(a.shape[0] for a in arrs))
@@ -80,4 +91,4 @@ def radar_to_pc_dep(radar_pcs, intrinsics, img_wh, calibs, trans_out, out_hw, ma
     pc_2d, pc_3d, counts = ops.radar_ingest(t(pc), t(cnt), t(K), img_wh, max_dist, z_offset, descending)
     calibs = np.asarray(calibs, np.float64).reshape(B, 3, 4)
     trans = np.broadcast_to(np.asarray(trans_out, np.float64), (B, 2, 3)).copy()
-    return ops.pillar_expand(pc_2d, pc_3d, counts, t(calibs), t(trans), out_hw, pillar_dims)
+    return _expand(pc_2d, pc_3d, counts, t(calibs), t(trans), out_hw, pillar_dims, roi_method)

@@ -427,6 +427,14 @@ int cf_topk_frustum(const float* heat, int C, int K, const float* depth, const f
                     float* pc_hm, float* pc_hm_nhwc4, void* pc_hm_split8, float* scores, int32_t* inds, int32_t* classes,
                     void* workspace, void* stream);
 
+/* cf_pc_hm_direct: middle fusion WITHOUT frustum association (MODEL.FRUSTUM = False): the radar map itself is the
+ * secondary heads' pc_hm.  replaces model/networks/base_model.py:69-79 (the in-place normalisation of the caller's pc_dep).
+ * pc_dep (B,3,H,W) fp32 NCHW: channel 0 is rewritten IN PLACE as 1 - x / max_pc_dist (fp32 division, then the subtraction:
+ * an empty pixel becomes 1.0), channels 1 and 2 are read only.  pc_hm_nhwc4 (B,H,W,4) fp32 and pc_hm_split8 (B,H,W,2,8)
+ * split-bf16, if not NULL (16-byte aligned), receive the three channels channels-last as cf_frustum_assoc writes them.  One pass. */
+int cf_pc_hm_direct(float* pc_dep, int B, int H, int W, float max_pc_dist, float* pc_hm_nhwc4, void* pc_hm_split8,
+                    void* stream);
+
 /* cf_pillar_expand: radar points -> pc_dep (B,3,H,W) by pillar expansion (fp64 geometry).
  * replaces dataset/generic_dataset.py:738-942 (processPointCloud / transformPointCloud /
  * getPcPillarsSize) + dataset/datasets/nuscenes.py:221-263 (getDepthMap / drawPcHeat).
@@ -439,6 +447,16 @@ int cf_pillar_expand(const double* pc_2d, const double* pc_3d, const int32_t* co
                      int max_n, int n_rows, const double* calib, const double* trans, int H, int W,
                      double pillar_h, double pillar_w, double pillar_l, float* pc_dep,
                      uint8_t* keep_mask, double* xy_out, void* stream);
+
+/* cf_radar_roi_expand: cf_pillar_expand's inputs and outputs for the other two DATASET.PC_ROI_METHOD values.
+ * method 1 = "points": replaces dataset/datasets/nuscenes.py:265-294 (drawPcPoints) - one pixel per kept point at the
+ *   truncated transformed coordinates; of several points on one pixel the last in order stays.
+ * method 2 = "heatmap": replaces dataset/generic_dataset.py:811-818 + utils/image.py:145-176 (getGaussianRadius, float64):
+ *   the square of radius int(gaussian_radius(250 / depth + 5)) around the truncated centre, clipped to the map; painted
+ *   in point order (later points overwrite earlier ones), as for pillars. */
+int cf_radar_roi_expand(const double* pc_2d, const double* pc_3d, const int32_t* counts, int B, int max_n,
+                        int n_rows, const double* calib, const double* trans, int H, int W, int method,
+                        float* pc_dep, uint8_t* keep_mask, double* xy_out, void* stream);
 
 /* cf_decode_gather: from K (index, class, score) peaks produce the 33-float detection rows of
  * model/decode.py:10-174 (fusionDecode): [score, classId, cx_n, cy_n, x1, y1, x2, y2, rot8, dim3,

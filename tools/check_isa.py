@@ -15,7 +15,7 @@ import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "centerfusiondetect3d_amd", "csrc")
 SOURCES = {"cf_conv3x3_f16.hip": ("conv3x3_f16x3_kernel",), "cf_heads.hip": ("head_patch_kernel", "head_patch16_kernel"),
-           "cf_gemm_f16.hip": ("dcn_f16x3_kernel", "conv_f16x3_kernel")}
+           "cf_gemm_f16.hip": ("dcn_f16x3_kernel", "conv_f16x3_kernel"), "cf_post.hip": ("pc_hm_direct_kernel",)}
 
 
 def functions(asm):
@@ -52,7 +52,8 @@ def violations(lines):
 EPILOGUE_KERNELS = ("conv_f16x3_kernel", "dcn_f16x3_kernel", "conv3x3_f16x3_kernel")
 # kernels whose MFMA loop must be free of scratch traffic (every instantiation the default path launches)
 # kernels of the default path: NO instantiation may use scratch at all (ScratchSize 0 in the compiler's resource summary)
-NO_SCRATCH = ("head_patch16_kernel", "head_patch_kernel", "dcn_f16x3_kernel", "conv3x3_f16x3_kernel", "conv_f16x3_kernel")
+NO_SCRATCH = ("head_patch16_kernel", "head_patch_kernel", "dcn_f16x3_kernel", "conv3x3_f16x3_kernel", "conv_f16x3_kernel",
+              "pc_hm_direct_kernel")
 
 
 def scratch_sizes(asm):
@@ -150,6 +151,12 @@ def main():
                 if sc:
                     print(f"{src}: {name[:90]}: {len(sc)} scratch ops inside an MFMA stream (same basic block, MFMAs on both sides)")
                     failed |= not report_only
+                if "pc_hm_direct_kernel" in name and "ILi4E" in name:
+                    # the 4-pixel form moves whole 16-byte vectors: 3 loads (one per channel plane), every store a dwordx4
+                    ops = [l.split()[0] for l in lines if re.match(r"\s+(global|flat|buffer)_(load|store)_", l)]
+                    wide = all(o.endswith("dwordx4") for o in ops) and sum("load" in o for o in ops) == 3
+                    print(f"{src}: {name[:90]}: {len(ops)} vector memory ops, all dwordx4: {wide}")
+                    failed |= not wide
                 v = violations(lines)
                 if v is None:
                     print(f"{src}: {name[:80]}: no pinned region")
