@@ -6,10 +6,10 @@ import os
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libcfhip.so")
 
-ABI_VERSION = 6      # CF_ABI_VERSION of include/cf_hip.h this binding was written against
+ABI_VERSION = 7      # CF_ABI_VERSION of include/cf_hip.h this binding was written against
 CF_MAX_SRC = 4
 ACT_NONE, ACT_RELU, ACT_SIGMOID_CLAMP, ACT_RAW_AND_SIGDEPTH = 0, 1, 2, 3
-LAYOUT_NHWC, LAYOUT_NCHW, LAYOUT_NHWC_SPLIT_BF16 = 0, 1, 2
+LAYOUT_NHWC, LAYOUT_NCHW = 0, 1
 
 _f = C.c_void_p  # device pointers travel as integers
 
@@ -101,14 +101,12 @@ class SerializeArgs(C.Structure):
 _i, _d = C.c_int, C.c_double
 SYMBOLS = {
     "cf_conv2d_fused": (_i, [C.POINTER(ConvArgs), _f]),
-    "cf_conv2d_bf16x3": (_i, [C.POINTER(ConvArgs), _f]),
     "cf_conv2d_f16x3": (_i, [C.POINTER(ConvArgs), _f]),
     "cf_conv3x3_f16x3": (_i, [C.POINTER(ConvArgs), _f]),
     "cf_conv3x3_root_f16x3": (_i, [C.POINTER(ConvArgs), C.POINTER(ConvArgs), C.POINTER(C.c_int32), _f]),
     "cf_conv3x3_proj_f16x3": (_i, [C.POINTER(ConvArgs), C.POINTER(C.c_int32), _f]),
     "cf_stem_fused": (_i, [C.POINTER(StemArgs), _f]),
     "cf_split_bf16": (_i, [_f, _f, C.c_long, _i, _i, _i, _f]),
-    "cf_head_tail": (_i, [C.POINTER(HeadTailArgs), _f]),
     "cf_head_fused": (_i, [C.POINTER(HeadFusedArgs), _f]),
     "cf_pack_feat_mx": (_i, [_f, _i, _f, C.c_long, _f]),
     "cf_pack_feat_mx_scaled": (_i, [_f, _i, _f, C.c_long, C.c_float, _f]),

@@ -22,7 +22,6 @@ COMMON = os.environ.get("CF_EXTRA_FLAGS", "").split() + ["-O3", "-std=c++17", "-
 # (source, extra flags).  cf_post: the index path must not fuse mul+add (bit-exact slice bounds).
 SOURCES = [
     ("cf_gemm.hip", []),
-    ("cf_gemm_bf16.hip", []),
     ("cf_gemm_f16.hip", []),
     ("cf_conv3x3_f16.hip", []),
     ("cf_stem.hip", []),

@@ -1,6 +1,7 @@
 // HBM-bound helpers of the DLA-34 / IDA-up graph: depthwise transposed-conv upsample (+ skip add),
-// 2x2 max-pool and the two layout changes at the module boundary.  All are one-pass streaming
-// kernels: 16 B per lane, channel-innermost (NHWC) so every wave-instruction touches whole lines.
+// 2x2 max-pool, the layout changes at the module boundary and the fp32 -> split-bf16 conversion.
+// All are one-pass streaming kernels: 16 B per lane, channel-innermost (NHWC) so every
+// wave-instruction touches whole lines.
 #include <stdlib.h>
 #include "cf_common.h"
 
@@ -224,6 +225,40 @@ __global__ __launch_bounds__(64) void spin_kernel(unsigned long long ticks) {
   while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
 }
 
+// ---- split-bf16: an fp32 value x carried as two bf16 numbers x = hi + lo (hi = rne(x), lo = rne(x - hi)): the operand format
+// of the head kernels (cf_heads.hip).  A pixel is [Cs hi][Cs lo] bf16 - the same HBM bytes as fp32.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
+  const __bf16 x = (__bf16)a, y = (__bf16)b;
+  return ((unsigned)__builtin_bit_cast(unsigned short, y) << 16) | __builtin_bit_cast(unsigned short, x);
+}
+__device__ __forceinline__ float bf16_round(float a) { return (float)(__bf16)a; }
+
+// fp32 NHWC [M][C] -> split-bf16 [M][2][Cs] (Cs >= C, channels C..Cs-1 zero), 8 channels per thread
+__global__ __launch_bounds__(256) void split_bf16_kernel(const float* __restrict__ x, unsigned char* __restrict__ out,
+                                                         long M, int C, int in_stride, int Cs) {
+  const int G = Cs / 8;
+  const long total = M * G;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long m = i / G;
+    const int c0 = (int)(i - m * G) * 8;
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (c0 + e < C) ? x[m * in_stride + c0 + e] : 0.0f;
+    u32x4 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = bf16_round(v[2 * e]), b = bf16_round(v[2 * e + 1]);
+      hi[e] = pack_bf16(a, b);
+      lo[e] = pack_bf16(v[2 * e] - a, v[2 * e + 1] - b);
+    }
+    unsigned char* o = out + ((size_t)m * 2 * Cs + c0) * 2;
+    *reinterpret_cast<u32x4*>(o) = hi;
+    *reinterpret_cast<u32x4*>(o + (size_t)Cs * 2) = lo;
+  }
+}
+
 inline int grid_for(long total) {
   long g = (total + 255) / 256;
   return (int)(g < 1 ? 1 : (g > 256 * 16 ? 256 * 16 : g));
@@ -319,4 +354,15 @@ extern "C" int cf_spin_us(int microseconds, void* stream) {
   CF_REQUIRE(microseconds > 0 && microseconds <= 100000, "cf_spin_us: %d us outside (0, 100000]", microseconds);
   hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long)microseconds * 100ull);
   return cf_check_launch("cf_spin_us");
+}
+
+extern "C" int cf_split_bf16(const float* x, void* out, long M, int C, int in_stride, int Cs, void* stream) {
+  CF_REQUIRE(x && out, "cf_split_bf16: null buffer");
+  CF_REQUIRE(M > 0 && C > 0 && in_stride >= C && Cs >= C && Cs % 8 == 0, "cf_split_bf16: bad geometry");
+  const long total = M * (Cs / 8);
+  long g = (total + 255) / 256;
+  if (g > 256 * 16) g = 256 * 16;
+  hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, x,
+                     reinterpret_cast<unsigned char*>(out), M, C, in_stride, Cs);
+  return cf_check_launch("cf_split_bf16");
 }

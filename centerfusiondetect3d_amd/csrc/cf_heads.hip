@@ -1,20 +1,25 @@
-// Fused tail of a detection head on the bf16 MFMA pipe (split operands, see cf_gemm_bf16.hip):
+// Whole detection heads in one launch on the bf16 MFMA pipe with SPLIT operands ("bf16x3"):
 //
-//     x (256 hidden channels of a 64-pixel tile)  ->  [ReLU(W_l x + b_l)] x n_hidden  ->  W_out x + b_out
+//     3x3 conv (64 [+3] -> 256) + ReLU  ->  [ReLU(W_l x + b_l)] x n_hidden  ->  W_out x + b_out (+ head activation)
 //
-// replaces the per-layer launches of model/networks/detectHeads.py:80-90 (1x1 256->256 + ReLU
-// layers) and :64-71 (1x1 256->n_out) whose only HBM-visible result is the small NCHW head map.
-// The hidden maps never return to HBM: one workgroup keeps its pixel tile [64 px][256 ch] (hi and lo
-// bf16 planes, 66 KiB) in LDS for the whole chain.
+// replaces the per-layer launches of model/networks/detectHeads.py:59-98 (3x3 first layer, 1x1 256->256 + ReLU
+// layers, 1x1 256->n_out) whose only HBM-visible result is the small NCHW head map: the hidden maps never reach HBM.
+//
+// Split operands: every fp32 value x is carried as two bf16 numbers x = hi + lo (hi = rne(x), lo = rne(x - hi), 16
+// significant bits together) and a product is evaluated as a*b ~= a_lo*b_hi + a_hi*b_lo + a_hi*b_hi (fp32 accumulate,
+// a_lo*b_lo dropped): three v_mfma_f32_16x16x32_bf16 per 32-deep k-step, relative error per product <= ~2^-17.  Used
+// for the heads only: they sit behind the DCN neck, so their rounding is not amplified (DESIGN.md section 4 "Numerics").
+// "split-bf16 NHWC" = a pixel is [C hi][C lo] bf16, the same HBM bytes as fp32 (cf_split_bf16, the DCN epilogue).
 //
 // GEMM orientation is SWAPPED with respect to the conv kernels: MFMA A-operand = weights
 // (rows = output channels), B-operand = activations (columns = pixels).  Consequences:
 //   * weights never touch LDS: they are pre-packed on the host in MFMA fragment order, so a wave's
-//     A fragment of one 16-deep k-step is ONE fully coalesced 1 KiB global load (L2-resident);
+//     A fragment of one 32-deep k-step is ONE fully coalesced 1 KiB global load (L2-resident);
 //   * no barrier inside a layer - only one between layers, when the tile is rewritten in place;
 //   * the accumulator has pixels on lanes, so the final NCHW store is coalesced along pixels.
-// Wave w of the 4 owns output channels [64w, 64w+64) x all 64 pixels (2x2 32x32 accumulators); in
-// the output layer the 4 waves split K instead and their partial sums are reduced through LDS.
+// In the hidden layers wave w of the 4 owns output channels [64w, 64w+64) x the 64 pixels of a half tile (4x4 16x16
+// accumulators) whose [64 px][256 ch] hi and lo planes (66 KiB) stay in LDS for the whole chain; in the output layer
+// the 4 waves split K instead and their partial sums are reduced through LDS.
 #include <stdlib.h>
 #include "cf_common.h"
 #include "cf_mx.h"
@@ -25,9 +30,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 hf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 hf16x32 __attribute__((ext_vector_type(32)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x6 __attribute__((ext_vector_type(6)));
 
 constexpr int HT_PX = 64;            // pixels per workgroup
 constexpr int HT_C = 256;            // hidden width
@@ -65,37 +68,8 @@ __device__ __forceinline__ const bf16x8* wfrag(const unsigned char* w, int rt, i
   return reinterpret_cast<const bf16x8*>(base + (unsigned)lane * 16u);
 }
 
-// accumulator (lane = pixel ct*32+li, reg r = channel 64w + 32rt + (r&3) + 8(r>>2) + 4h) -> ReLU(acc + b)
-// -> split bf16 -> LDS tile [plane][px][528 B]
-#ifdef CF_LEGACY_HEADS   // (32x32x16 / slot-table head kernels of rounds 1-3: nothing dispatches them in the default build)
-__device__ __forceinline__ void store_hidden_tile(unsigned char* xt, const f32x16 (&acc)[2][2], const float* bias,
-                                                  int wave, int li, int h) {
-#pragma unroll
-  for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int ch = wave * 64 + rt * 32 + 8 * g + 4 * h;
-        const f32x4 bb = *reinterpret_cast<const f32x4*>(bias + ch);
-        float v[4], hi[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          v[e] = fmaxf(acc[rt][ct][g * 4 + e] + bb[e], 0.0f);
-          hi[e] = bf16_rne(v[e]);
-        }
-        unsigned char* o = xt + (ct * 32 + li) * HT_ROWB + ch * 2;
-        const u32x2 ph = {pack2(hi[0], hi[1]), pack2(hi[2], hi[3])};
-        const u32x2 pl = {pack2(v[0] - hi[0], v[1] - hi[1]), pack2(v[2] - hi[2], v[3] - hi[3])};
-        *reinterpret_cast<u32x2*>(o) = ph;
-        *reinterpret_cast<u32x2*>(o + HT_PLANE) = pl;
-      }
-}
-
-// the same from 16x16 accumulators (v_mfma_f32_16x16x32_bf16: lane = pixel ct*16 + (l & 15), reg r = channel
-// 64w + 16rt + 4(l >> 4) + r) of one 64-pixel half tile
-#endif  // CF_LEGACY_HEADS
-
+// 16x16 accumulators of one 64-pixel half tile (v_mfma_f32_16x16x32_bf16: lane = pixel ct*16 + (l & 15), reg r = channel
+// 64w + 16rt + 4(l >> 4) + r) -> ReLU(acc + b) -> split bf16 -> LDS tile [plane][px][528 B]
 template <bool SCALED = false>
 __device__ __forceinline__ void store_hidden_tile16(unsigned char* xt, const f32x4 (&acc)[4][4], const float* bias,
                                                     int wave, int lane, float sc = 1.0f, int pxcol = -1) {
@@ -122,16 +96,6 @@ __device__ __forceinline__ void store_hidden_tile16(unsigned char* xt, const f32
 }
 
 // pixel index inside a 64-pixel tile -> (image, pixel inside the image); false = outside
-struct FlatMap {       // 64 consecutive pixels of the flattened (B*H*W) index space
-  int m0, M, HW;
-  __device__ __forceinline__ bool operator()(int px, int& b, int& pix) const {
-    const int m = m0 + px;
-    if (m >= M) return false;
-    b = m / HW;
-    pix = m - b * HW;
-    return true;
-  }
-};
 struct TileMap {       // 64 pixels of a tile at (y0, x0) of image b: 4 rows of 16 (sh = 4) or 8 rows of 8 (sh = 3)
   int b, y0, x0, H, W, sh = 4;
   __device__ __forceinline__ bool operator()(int px, int& bb, int& pix) const {
@@ -143,130 +107,9 @@ struct TileMap {       // 64 pixels of a tile at (y0, x0) of image b: 4 rows of 
   }
 };
 
-// 4 per-wave partial output tiles [32 n][64 px] -> LDS -> sum + bias + activation -> NCHW
-#ifdef CF_LEGACY_HEADS   // (32x32x16 / slot-table head kernels of rounds 1-3: nothing dispatches them in the default build)
-template <class PixMap>
-__device__ __forceinline__ void reduce_and_store(const HeadTailK& p, unsigned char* xt, const f32x16 (&oacc)[2],
-                                                 int head, const PixMap& pm) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, h = lane >> 5;
-  float* red = reinterpret_cast<float*>(xt);
-#pragma unroll
-  for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int n = (r & 3) + 8 * (r >> 2) + 4 * h;
-      red[(wave * 32 + n) * HT_PX + ct * 32 + li] = oacc[ct][r];
-    }
-  __syncthreads();
-  const int n_out = p.n_out[head], act = p.act[head];
-  const float* bo = p.b_out[head];
-  float* out = p.out[head];
-  float* out2 = p.out2[head];
-  const int px = tid & 63;
-  int b, pix;
-  if (pm(px, b, pix)) {
-    for (int n = tid >> 6; n < n_out; n += 4) {
-      const float raw = red[n * HT_PX + px] + red[(32 + n) * HT_PX + px] + red[(64 + n) * HT_PX + px] +
-                        red[(96 + n) * HT_PX + px] + bo[n];
-      const size_t o = ((size_t)b * n_out + n) * p.HW + pix;
-      float v = raw;
-      if (act == CF_ACT_RELU) v = fmaxf(raw, 0.0f);
-      else if (act == CF_ACT_SIGMOID_CLAMP) v = fminf(fmaxf(cf_sigmoid(raw), 1e-4f), 1.0f - 1e-4f);
-      out[o] = v;
-      if (act == CF_ACT_RAW_AND_SIGDEPTH) out2[o] = 1.0f / (cf_sigmoid(raw) + 1e-6f) - 1.0f;
-    }
-  }
-}
-
-// Hidden layers + output layer on a pixel tile that is already in LDS (xt).  All 256 threads.
-template <class PixMap>
-__device__ __forceinline__ void head_tail_from_lds(const HeadTailK& p, unsigned char* xt, int head, const PixMap& pm) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, h = lane >> 5;
-
-  // ---- hidden layers: acc[rt][ct] = W[64w + 32rt .. +32][:] . X[:][32ct .. +32]
-  for (int l = 0; l < p.n_hidden; ++l) {
-    const unsigned char* w = p.w_hidden[head][l];
-    const float* bias = p.b_hidden[head][l];
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-    bf16x8 wh[3][2], wl[3][2];  // [set = ks % 3][rt]: three k-steps ahead
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int rt = 0; rt < 2; ++rt) {
-        wh[t][rt] = *wfrag(w, wave * 2 + rt, t, 0, 16, lane);
-        wl[t][rt] = *wfrag(w, wave * 2 + rt, t, 1, 16, lane);
-      }
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks) {
-      const int cur = ks % 3;
-      bf16x8 xh[2], xl[2];
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct) {
-        const unsigned char* row = xt + (ct * 32 + li) * HT_ROWB + (ks * 16 + h * 8) * 2;
-        xh[ct] = *reinterpret_cast<const bf16x8*>(row);
-        xl[ct] = *reinterpret_cast<const bf16x8*>(row + HT_PLANE);
-      }
-#pragma unroll
-      for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-          acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[cur][rt], xh[ct], acc[rt][ct], 0, 0, 0);
-          acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[cur][rt], xl[ct], acc[rt][ct], 0, 0, 0);
-          acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[cur][rt], xh[ct], acc[rt][ct], 0, 0, 0);
-        }
-      if (ks + 3 < 16) {
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt) {
-          wh[cur][rt] = *wfrag(w, wave * 2 + rt, ks + 3, 0, 16, lane);
-          wl[cur][rt] = *wfrag(w, wave * 2 + rt, ks + 3, 1, 16, lane);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);   // keep the look-ahead loads from sinking to their first use
-    }
-    __syncthreads();  // every wave has read the whole tile: rewrite it in place
-    store_hidden_tile(xt, acc, bias, wave, li, h);
-    __syncthreads();
-  }
-
-  // ---- output layer: out[n][px] = sum_k Wout[n][k] X[k][px]; wave w takes k in [64w, 64w+64)
-  f32x16 oacc[2];
-#pragma unroll
-  for (int b = 0; b < 2; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) oacc[b][r] = 0.0f;
-  {
-    const unsigned char* w = p.w_out[head];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int ks = wave * 4 + s;
-      const bf16x8 ah = *wfrag(w, 0, ks, 0, 16, lane), al = *wfrag(w, 0, ks, 1, 16, lane);
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct) {
-        const unsigned char* row = xt + (ct * 32 + li) * HT_ROWB + (ks * 16 + h * 8) * 2;
-        const bf16x8 xh = *reinterpret_cast<const bf16x8*>(row);
-        const bf16x8 xl = *reinterpret_cast<const bf16x8*>(row + HT_PLANE);
-        oacc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh, oacc[ct], 0, 0, 0);
-        oacc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl, oacc[ct], 0, 0, 0);
-        oacc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh, oacc[ct], 0, 0, 0);
-      }
-    }
-  }
-  __syncthreads();  // tile no longer needed: reuse LDS for the 4 partial sums [wave][n 32][px 64]
-  reduce_and_store(p, xt, oacc, head, pm);
-}
-
-// The same chain on v_mfma_f32_16x16x32_bf16 (weights packed by pack_fragments16: w_hidden [16 rt][8 ks], w_out one
-// 16-row tile): wave w owns channels [64w, 64w+64) x 64 pixels as 4 x 4 accumulators of 16 x 16; a k-step is 32 deep.
-#endif  // CF_LEGACY_HEADS
-
+// Hidden layers + output layer on a pixel tile that is already in LDS (xt).  All 256 threads.  Weights packed by
+// pack_fragments16: w_hidden [16 rt][8 ks], w_out one 16-row tile; wave w owns channels [64w, 64w+64) x 64 pixels as
+// 4 x 4 accumulators of 16 x 16; a k-step is 32 deep.
 template <class PixMap>
 __device__ __forceinline__ void head_tail_from_lds16(const HeadTailK& p, unsigned char* xt, int head, const PixMap& pm) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -378,249 +221,24 @@ __device__ __forceinline__ void head_tail_from_lds16(const HeadTailK& p, unsigne
   }
 }
 
-#ifdef CF_LEGACY_HEADS   // (32x32x16 / slot-table head kernels of rounds 1-3: nothing dispatches them in the default build)
-// Tail only: the 256-channel hidden tile comes from a split-bf16 tensor in HBM.
-__global__ __launch_bounds__(256) void head_tail_kernel(HeadTailK p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char xt[];  // [2 planes][64 px][528 B]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, h = lane >> 5;
-  const int tiles = (p.M + HT_PX - 1) / HT_PX;
-  const int head = blockIdx.x / tiles, tile = blockIdx.x - head * tiles;
-  const int m0 = tile * HT_PX;
-  const int cb = p.c_base[head];
-
-  if (p.n_hidden > 0) {
-    // all 16 requests of a thread are issued before the first LDS write: the whole 64 KiB tile is
-    // in flight at once
-    u32x4 v[16];
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-      const int i = tid + it * 256;
-      const int unit = i & 31, plane = (i >> 5) & 1, px = i >> 6;
-      const int m = m0 + px;
-      v[it] = u32x4{0u, 0u, 0u, 0u};
-      if (m < p.M)
-        v[it] = *reinterpret_cast<const u32x4*>(p.x + (((size_t)m * 2 + plane) * p.x_stride + cb) * 2 + unit * 16);
-    }
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-      const int i = tid + it * 256;
-      const int unit = i & 31, plane = (i >> 5) & 1, px = i >> 6;
-      *reinterpret_cast<u32x4*>(xt + plane * HT_PLANE + px * HT_ROWB + unit * 16) = v[it];
-    }
-    __syncthreads();
-    head_tail_from_lds(p, xt, head, FlatMap{m0, p.M, p.HW});
-    return;
-  }
-  // no hidden layer: the B fragments (pixels x this wave's 64 input channels) come straight from
-  // HBM - every byte of the tile is read exactly once by exactly one lane, no LDS staging
-  f32x16 oacc[2];
-#pragma unroll
-  for (int b = 0; b < 2; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) oacc[b][r] = 0.0f;
-  const unsigned char* w = p.w_out[head];
-  bf16x8 xh[2][4], xl[2][4];
-#pragma unroll
-  for (int ct = 0; ct < 2; ++ct) {
-    const int m = m0 + ct * 32 + li;
-    const unsigned char* row = p.x + ((size_t)(m < p.M ? m : 0) * 2 * p.x_stride + cb) * 2;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int k = (wave * 4 + s) * 16 + h * 8;
-      xh[ct][s] = *reinterpret_cast<const bf16x8*>(row + k * 2);
-      xl[ct][s] = *reinterpret_cast<const bf16x8*>(row + ((size_t)p.x_stride + k) * 2);
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int ks = wave * 4 + s;
-    const bf16x8 ah = *wfrag(w, 0, ks, 0, 16, lane), al = *wfrag(w, 0, ks, 1, 16, lane);
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-      oacc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[ct][s], oacc[ct], 0, 0, 0);
-      oacc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl[ct][s], oacc[ct], 0, 0, 0);
-      oacc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[ct][s], oacc[ct], 0, 0, 0);
-    }
-  }
-  reduce_and_store(p, xt, oacc, head, FlatMap{m0, p.M, p.HW});
-}
-#endif  // CF_LEGACY_HEADS
-
 // ---------------------------------------------------------------------------------------------
-// Whole head in one launch: 3x3 conv (64 [+3] -> 256) + ReLU, then the tail above.  The first layer
-// is the same swapped GEMM: weights as pre-packed A fragments straight from L2 (4 k-steps ahead in
-// registers), the pixel operand (implicit im2col of the split-bf16 feature map, 8-channel slots) is
-// staged per 32-deep chunk through a small double-buffered LDS tile [64 px][32 k] shared by the 4
-// waves - one barrier per chunk.  The 256-channel hidden map is born in LDS and never reaches HBM.
+// Whole head on a 2-D PATCH: one workgroup owns an 8 x 16 (or 16 x 8) pixel tile (128 px) of one image.  The
+// (8+2) x (16+2) input patch - all 64 feature channels (and the 8-channel pc_hm plane pair) in split-bf16 - is copied
+// to LDS once, zero-filled outside the image, and all 9 taps read their B fragments from it at compile-time offsets:
+// no slot table, no barrier and no staging inside the K loop.  A wave owns 64 hidden channels x 128 pixels as 4 x 8
+// accumulators of 16 x 16 (v_mfma_f32_16x16x32_bf16); a k-step is 32 deep = half the channels of one tap (or four
+// taps of the pc_hm plane pair).  Under the chip's power management a dense MFMA loop on random data holds a higher
+// clock with the 16x16x32 shape than with 32x32x16 at equal cycles per FLOP: measured on this part 1.72 vs 1.51
+// PFLOP/s with every operand re-read from LDS (tools/micro/mfma_shape.hip, MI355X_MICROARCH.md "DVFS give-back"
+// item 7) - and this kernel is bound by exactly that loop.  Weights come as [16-row tile][k32 step][hi|lo][lane][8]
+// fragments (packing.pack_fragments16), one k-step ahead in registers.  With n_hidden == 0 the 256 -> n_out layer
+// runs straight from the accumulator registers: ReLU(acc + b) split to bf16 IS a B fragment - two stacked 16 x 16
+// tiles give a lane 4 + 4 channels of one pixel - if w_out is packed in that k order
+// (pack_fragments16(acc_order=True)); the four waves' partial sums meet in LDS; n_out <= 16.
 // ---------------------------------------------------------------------------------------------
-struct HeadFusedK {
-  HeadTailK t;
-  const unsigned char* src[2];      // split-bf16 NHWC sources of the 3x3 layer (feat, pc_hm)
-  int src_c[2];
-  const cf_slot* slots;             // 8-channel slots, 4 per chunk, n_chunks even
-  int n_chunks, H, W;
-  const unsigned char* w_first[CF_MAX_HEADS];  // fragment-packed [8 rt][K_pad/16 ks]
-  const float* b_first[CF_MAX_HEADS];
-};
-
-constexpr int HF_ROWB = 80;                       // 32 bf16 + 16 B pad per pixel row per plane
-constexpr int HF_PLANE = HT_PX * HF_ROWB;         // 5120
-constexpr int HF_BUF = 2 * HF_PLANE;              // 10240 per chunk buffer
-constexpr int HF_MAX_CHUNKS = 64;
-constexpr int HF_LDS = HT_LDS + HF_MAX_CHUNKS * 4 * (int)sizeof(cf_slot);   // tile area + slot table
-
-#ifdef CF_LEGACY_HEADS   // (the slot-table head kernel)
-__global__ __launch_bounds__(256) void head_fused_kernel(HeadFusedK q) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char xt[];  // B chunk buffers, later the hidden tile
-  const HeadTailK& p = q.t;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, h = lane >> 5;
-  const int tiles = (p.M + HT_PX - 1) / HT_PX;
-  const int head = blockIdx.x / tiles, tile = blockIdx.x - head * tiles;
-  const int m0 = tile * HT_PX;
-  const unsigned char* w1 = q.w_first[head];
-  const int n_ks = q.n_chunks * 2;
-
-  // staging role of this thread: one pixel row, one 8-channel unit, both planes
-  const int spx = tid >> 2, su = tid & 3;
-  int y0, x0, boff;
-  {
-    const int m = m0 + spx;
-    if (m < p.M) {
-      const int b = m / p.HW, rem = m - b * p.HW;
-      y0 = rem / q.W;
-      x0 = rem - y0 * q.W;
-      boff = b * p.HW;
-    } else {
-      y0 = -(1 << 28);
-      x0 = 0;
-      boff = 0;
-    }
-  }
-  // slot table -> LDS (behind the tile area): a per-chunk global read of it would put a dependent
-  // L2 round trip (and a vmcnt(0) drain of the weight prefetches) in front of every staging load
-  cf_slot* lds_slots = reinterpret_cast<cf_slot*>(xt + HT_LDS);
-  for (int i = tid; i < q.n_chunks * 4; i += 256) lds_slots[i] = q.slots[i];
-  __syncthreads();
-  u32x4 sh, sl;
-  auto load_b = [&](int c) {
-    const cf_slot s = lds_slots[c * 4 + su];
-    const int src = __builtin_amdgcn_readfirstlane(lds_slots[c * 4].src);
-    const unsigned char* sp = src == 1 ? q.src[1] : q.src[0];
-    const int sc = src == 1 ? q.src_c[1] : q.src_c[0];
-    const int y = y0 + s.dy, x = x0 + s.dx;
-    const bool ok = (s.c_off >= 0) && ((unsigned)y < (unsigned)q.H) && ((unsigned)x < (unsigned)q.W);
-    sh = u32x4{0u, 0u, 0u, 0u};
-    sl = sh;
-    if (ok) {
-      const unsigned char* a = sp + ((size_t)(boff + y * q.W + x) * (2 * sc) + s.c_off) * 2;
-      sh = *reinterpret_cast<const u32x4*>(a);
-      sl = *reinterpret_cast<const u32x4*>(a + (size_t)sc * 2);
-    }
-  };
-  auto store_b = [&](unsigned char* buf) {
-    *reinterpret_cast<u32x4*>(buf + spx * HF_ROWB + su * 16) = sh;
-    *reinterpret_cast<u32x4*>(buf + HF_PLANE + spx * HF_ROWB + su * 16) = sl;
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-
-  // weight fragments, 4 k-steps (= 2 chunks) ahead: set t holds k-step (4n + t)
-  bf16x8 wh[4][2], wl[4][2];
-  auto load_w = [&](bf16x8 (&dh)[2], bf16x8 (&dl)[2], int ks) {
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt) {
-      dh[rt] = *wfrag(w1, wave * 2 + rt, ks, 0, n_ks, lane);
-      dl[rt] = *wfrag(w1, wave * 2 + rt, ks, 1, n_ks, lane);
-    }
-  };
-  auto mma_kstep = [&](const unsigned char* buf, int s, const bf16x8 (&ah)[2], const bf16x8 (&al)[2]) {
-    bf16x8 xh[2], xl[2];
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-      const unsigned char* row = buf + (ct * 32 + li) * HF_ROWB + s * 32 + h * 16;
-      xh[ct] = *reinterpret_cast<const bf16x8*>(row);
-      xl[ct] = *reinterpret_cast<const bf16x8*>(row + HF_PLANE);
-    }
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct) {
-        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[rt], xh[ct], acc[rt][ct], 0, 0, 0);
-        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[rt], xl[ct], acc[rt][ct], 0, 0, 0);
-        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[rt], xh[ct], acc[rt][ct], 0, 0, 0);
-      }
-  };
-
-  load_b(0);
-  load_w(wh[0], wl[0], 0);
-  load_w(wh[1], wl[1], 1);
-  load_w(wh[2], wl[2], 2);
-  load_w(wh[3], wl[3], 3);
-  store_b(xt);
-  load_b(1);
-  __syncthreads();
-  // two chunks (four k-steps) per iteration so the four fragment sets are addressed statically.
-  // Straight-line body (look-ahead indices clamped, not branched) with a sched_barrier after every
-  // k-step: without it the compiler sinks the prefetch loads down to their first use.
-  const int last_c = q.n_chunks - 1;
-  for (int c = 0; c < q.n_chunks; c += 2) {
-    unsigned char* b0 = xt;
-    unsigned char* b1 = xt + HF_BUF;
-    const int ks = c * 2;
-    // chunk c  (buffer 0)
-    mma_kstep(b0, 0, wh[0], wl[0]);
-    load_w(wh[0], wl[0], min(ks + 4, n_ks - 1));
-    __builtin_amdgcn_sched_barrier(0);
-    mma_kstep(b0, 1, wh[1], wl[1]);
-    load_w(wh[1], wl[1], min(ks + 5, n_ks - 1));
-    store_b(b1);                       // chunk c+1 (requested a chunk ago)
-    load_b(min(c + 2, last_c));
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
-    // chunk c+1 (buffer 1)
-    mma_kstep(b1, 0, wh[2], wl[2]);
-    load_w(wh[2], wl[2], min(ks + 6, n_ks - 1));
-    __builtin_amdgcn_sched_barrier(0);
-    mma_kstep(b1, 1, wh[3], wl[3]);
-    load_w(wh[3], wl[3], min(ks + 7, n_ks - 1));
-    store_b(b0);                       // chunk c+2 (a repeat of the last chunk at the end: never read)
-    load_b(min(c + 3, last_c));
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
-  }
-  // hidden = ReLU(acc + b) -> LDS tile (the staging buffers are dead: last barrier above)
-  store_hidden_tile(xt, acc, q.b_first[head], wave, li, h);
-  __syncthreads();
-  head_tail_from_lds(p, xt, head, FlatMap{m0, p.M, p.HW});
-}
-
-
-#endif  // CF_LEGACY_HEADS
-
-// ---------------------------------------------------------------------------------------------
-// Whole head with n_hidden == 0 on a 2-D PATCH: one workgroup owns an 8 x 16 pixel tile (128 px) of
-// one image and one head.  The (8+2) x (16+2) input patch - all 64 feature channels (and the 8-channel
-// pc_hm plane pair) in split-bf16 - is copied to LDS once, zero-filled outside the image, and all 9
-// taps x 4 slices read their B fragments from it at compile-time offsets: no slot table, no barrier
-// and no staging inside the K loop.  A wave owns 64 hidden channels x 128 pixels, so the first-layer
-// weights (the dominant L2 stream of the 64-pixel kernel above) are fetched once per 128 pixels.
-// The 256 -> n_out layer runs straight from the accumulator registers: ReLU(acc + b) split to bf16 IS
-// a B fragment if the output weights are packed with the matching k permutation (w_out_perm: position
-// 8h + j of a 16-group holds channel 4h + (j & 3) + 8(j >> 2)); the four waves' partial sums meet in LDS.
-// ---------------------------------------------------------------------------------------------
-constexpr int HP_TH = 8, HP_TW = 16, HP_PW = HP_TW + 2, HP_ROWS = (HP_TH + 2) * HP_PW;   // 180 patch rows
-constexpr int HP_PX = HP_TH * HP_TW;                                                    // 128
-constexpr int HP_RED = 4 * 32 * HP_PX * 4;                                              // 64 KiB of partial sums
-constexpr int HP_LDS = HT_LDS > HP_RED ? HT_LDS : HP_RED;   // patch (<= 55 KiB) / partial sums / 64-pixel hidden tile
-constexpr int HP16_RED = 4 * 16 * HP_PX * 4;   // 16x16x32 kernel: partial sums [wave][16][128] BEHIND the patch
+constexpr int HP_ROWS = (8 + 2) * (16 + 2);    // 180 patch rows (either tile orientation)
+constexpr int HP_PX = 8 * 16;                  // 128 pixels per tile
+constexpr int HP16_RED = 4 * 16 * HP_PX * 4;   // partial sums [wave][16][128] BEHIND the patch
 constexpr int hp16_patch_bytes(bool pc) { return HP_ROWS * (4 * 64 + (pc ? 32 : 0) + 16); }   // 48,960 / 54,720
 // without pc_hm: 48,960 + 32,768 = 81,728 B <= half of the CU's 160 KiB: still two workgroups per CU
 constexpr int hp16_lds(bool pc, bool hidden) {
@@ -629,256 +247,17 @@ constexpr int hp16_lds(bool pc, bool hidden) {
 
 struct HeadPatchK {
   HeadTailK t;
-  const unsigned char* src[2];
+  const unsigned char* src[2];               // split-bf16 NHWC sources of the 3x3 layer (feat or its mx rows, pc_hm)
   int src_c[2];
   int H, W, tiles_x, tiles_y, n_ks;
-  int group;                                 // 0: head-major grid; g > 0: tile-major within groups of g heads (32x32x16 kernel)
-  int hloop;                                 // 16x16x32 kernel: consecutive heads one workgroup walks on its patch
+  int group;                                 // not read (always 0): keeps the kernel argument layout
+  int hloop;                                 // consecutive heads one workgroup walks on its patch
   const unsigned char* w_first[CF_MAX_HEADS];
   const float* b_first[CF_MAX_HEADS];
   const unsigned char* w_out_perm[CF_MAX_HEADS];
   float first_scale[CF_MAX_HEADS];           // MX kernel: 2^-(s+4) of head i's first layer
 };
 
-#ifdef CF_LEGACY_HEADS   // (32x32x16 / slot-table head kernels of rounds 1-3: nothing dispatches them in the default build)
-template <int NS, bool PC>
-__global__ __launch_bounds__(256, 2) void head_patch_kernel(HeadPatchK q) {
-  constexpr int ROWB = NS * 64 + (PC ? 32 : 0) + 16;     // odd multiple of 16 B
-  constexpr int NK = 9 * NS + (PC ? 5 : 0);              // k-steps of the first layer
-  extern __shared__ __attribute__((aligned(16))) unsigned char xt[];
-  const HeadTailK& p = q.t;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, h = lane >> 5;
-  const int per_img = q.tiles_x * q.tiles_y;
-  const int per_head = per_img * (p.M / p.HW);
-  int head, rem;
-  if (q.group == 0) {                        // head-major: every tile of head 0, then head 1, ...
-    head = blockIdx.x / per_head;
-    rem = blockIdx.x - head * per_head;
-  } else {
-    // tile-major inside groups of `group` heads, XCD-aware: the hardware deals workgroups round-robin over the 8
-    // XCDs, so the blocks one XCD sees (b, b + 8, ...) are made to walk (tile, head of the group) with the head
-    // fastest - the heads of a tile then run back to back on ONE XCD and all but the first find the patch in L2
-    const int g = q.group;
-    const int n_groups = (p.n_heads + g - 1) / g;
-    const int per_group = per_head * g;      // (the last group may be short: its surplus blocks exit)
-    const int grp = blockIdx.x / per_group;
-    const int lb = cf_xcd_remap(blockIdx.x - grp * per_group, per_group);
-    (void)n_groups;
-    rem = lb / g;
-    head = grp * g + (lb - rem * g);
-    if (head >= p.n_heads) return;
-  }
-  const int b = rem / per_img;
-  rem -= b * per_img;
-  const int y0 = (rem / q.tiles_x) * HP_TH, x0 = (rem % q.tiles_x) * HP_TW;
-  const unsigned char* w1 = q.w_first[head];
-
-  // ---- patch -> LDS (one pass, every load in flight before the first LDS write)
-  {
-    constexpr int UPR = NS * 4;                            // 16-byte units per row: hi plane then lo plane
-    constexpr int NIT = (HP_ROWS * UPR + 255) / 256;
-    u32x4 v[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int idx = tid + it * 256;
-      const int row = idx / UPR, u = idx % UPR;
-      const int y = y0 - 1 + row / HP_PW, x = x0 - 1 + row % HP_PW;
-      v[it] = u32x4{0u, 0u, 0u, 0u};
-      if (row < HP_ROWS && (unsigned)y < (unsigned)q.H && (unsigned)x < (unsigned)q.W)
-        v[it] = *reinterpret_cast<const u32x4*>(q.src[0] + ((size_t)(b * p.HW + y * q.W + x) * 2 * q.src_c[0]) * 2 +
-                                                (u / (NS * 2)) * q.src_c[0] * 2 + (u % (NS * 2)) * 16);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int idx = tid + it * 256;
-      const int row = idx / UPR, u = idx % UPR;
-      const int plane = u / (NS * 2), uu = u % (NS * 2);
-      if (row < HP_ROWS) *reinterpret_cast<u32x4*>(xt + row * ROWB + (uu >> 1) * 64 + plane * 32 + (uu & 1) * 16) = v[it];
-    }
-    if (PC) {
-      for (int idx = tid; idx < HP_ROWS * 2; idx += 256) {
-        const int row = idx >> 1, plane = idx & 1;
-        const int y = y0 - 1 + row / HP_PW, x = x0 - 1 + row % HP_PW;
-        u32x4 w = {0u, 0u, 0u, 0u};
-        if ((unsigned)y < (unsigned)q.H && (unsigned)x < (unsigned)q.W)
-          w = *reinterpret_cast<const u32x4*>(q.src[1] + ((size_t)(b * p.HW + y * q.W + x) * 2 + plane) * q.src_c[1] * 2);
-        *reinterpret_cast<u32x4*>(xt + row * ROWB + NS * 64 + plane * 16) = w;
-      }
-    }
-  }
-
-  int rowb[4];                               // LDS byte offset of this lane's pixel row (tap (-1,-1)) + k half
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) {
-    const int pl = ct * 32 + li;
-    rowb[ct] = ((pl >> 4) * HP_PW + (pl & 15)) * ROWB + h * 16;
-  }
-  f32x16 acc[2][4];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][c][r] = 0.0f;
-
-  bf16x8 wh[3][2], wl[3][2];                 // weight fragments three k-steps ahead: set ks % 3
-  auto load_w = [&](bf16x8 (&dh)[2], bf16x8 (&dl)[2], int ks) {
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt) {
-      dh[rt] = *wfrag(w1, wave * 2 + rt, ks, 0, q.n_ks, lane);
-      dl[rt] = *wfrag(w1, wave * 2 + rt, ks, 1, q.n_ks, lane);
-    }
-  };
-#pragma unroll
-  for (int t = 0; t < 3; ++t) load_w(wh[t], wl[t], t);
-  __syncthreads();
-
-#pragma unroll
-  for (int ks = 0; ks < NK; ++ks) {
-    bf16x8 xh[4], xl[4];
-    if (ks < 9 * NS) {
-      constexpr int dummy = 0;
-      (void)dummy;
-      const int tap = ks / NS, sl = ks % NS;
-      const int off = ((tap / 3) * HP_PW + tap % 3) * ROWB + sl * 64;
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        xh[ct] = *reinterpret_cast<const bf16x8*>(xt + rowb[ct] + off);
-        xl[ct] = *reinterpret_cast<const bf16x8*>(xt + rowb[ct] + off + 32);
-      }
-    } else {                                 // pc_hm: k half h of step i is tap 2i + h (8 channels each)
-      const int i = ks - 9 * NS;
-      const int t0 = 2 * i, t1 = 2 * i + 1 < 9 ? 2 * i + 1 : 8;
-      const int o0 = ((t0 / 3) * HP_PW + t0 % 3) * ROWB, o1 = ((t1 / 3) * HP_PW + t1 % 3) * ROWB;
-      const int off = (h ? o1 - 16 : o0) + NS * 64;
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        xh[ct] = *reinterpret_cast<const bf16x8*>(xt + rowb[ct] + off);
-        xl[ct] = *reinterpret_cast<const bf16x8*>(xt + rowb[ct] + off + 16);
-      }
-    }
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct)
-        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[ks % 3][rt], xh[ct], acc[rt][ct], 0, 0, 0);
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct)
-        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[ks % 3][rt], xl[ct], acc[rt][ct], 0, 0, 0);
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct)
-        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[ks % 3][rt], xh[ct], acc[rt][ct], 0, 0, 0);
-    if (ks + 3 < NK) load_w(wh[ks % 3], wl[ks % 3], ks + 3);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-
-  if (p.n_hidden > 0) {
-    // hidden layers need all 256 channels of a pixel: the two 64-pixel halves of the tile go through
-    // the LDS-resident chain of cf_head_tail one after the other (LDS stays at 66 KiB: 2 workgroups/CU)
-    __syncthreads();                         // every wave is done with the patch
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      f32x16 a2[2][2];
-#pragma unroll
-      for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) a2[rt][ct] = acc[rt][2 * half + ct];
-      store_hidden_tile(xt, a2, q.b_first[head], wave, li, h);
-      __syncthreads();
-      head_tail_from_lds(p, xt, head, TileMap{b, y0 + 4 * half, x0, q.H, q.W});
-      __syncthreads();
-    }
-    return;
-  }
-
-  // ---- output layer from registers: this wave's 64 hidden channels = 4 k-steps of 16
-  f32x16 oacc[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) oacc[c][r] = 0.0f;
-  {
-    const float* b1 = q.b_first[head] + wave * 64 + 4 * h;
-    const unsigned char* wo = q.w_out_perm[head];
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj) {
-        const int ks2 = wave * 4 + rt * 2 + jj;
-        const bf16x8 ah = *wfrag(wo, 0, ks2, 0, 16, lane), al = *wfrag(wo, 0, ks2, 1, 16, lane);
-        const f32x4 ba = *reinterpret_cast<const f32x4*>(b1 + rt * 32 + 16 * jj);
-        const f32x4 bb = *reinterpret_cast<const f32x4*>(b1 + rt * 32 + 16 * jj + 8);
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) {
-          float v[8], hi[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            v[j] = fmaxf(acc[rt][ct][8 * jj + j] + (j < 4 ? ba[j] : bb[j - 4]), 0.0f);
-            hi[j] = bf16_rne(v[j]);
-          }
-          const u32x4 ph = {pack2(hi[0], hi[1]), pack2(hi[2], hi[3]), pack2(hi[4], hi[5]), pack2(hi[6], hi[7])};
-          const u32x4 pl = {pack2(v[0] - hi[0], v[1] - hi[1]), pack2(v[2] - hi[2], v[3] - hi[3]),
-                            pack2(v[4] - hi[4], v[5] - hi[5]), pack2(v[6] - hi[6], v[7] - hi[7])};
-          const bf16x8 xh = __builtin_bit_cast(bf16x8, ph), xl = __builtin_bit_cast(bf16x8, pl);
-          oacc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh, oacc[ct], 0, 0, 0);
-          oacc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl, oacc[ct], 0, 0, 0);
-          oacc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh, oacc[ct], 0, 0, 0);
-        }
-      }
-  }
-  __syncthreads();                           // every wave is done with the patch: reuse LDS for the partial sums
-  const int n_out = p.n_out[head], act = p.act[head];
-  float* red = reinterpret_cast<float*>(xt); // [wave][n 32][px 128]
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int n = (r & 3) + 8 * (r >> 2) + 4 * h;
-      if (n < n_out) red[(wave * 32 + n) * HP_PX + ct * 32 + li] = oacc[ct][r];
-    }
-  __syncthreads();
-  {
-    const int px = tid & (HP_PX - 1);
-    const int y = y0 + (px >> 4), x = x0 + (px & 15);
-    if (y < q.H && x < q.W) {
-      const float* bo = p.b_out[head];
-      float* out = p.out[head];
-      float* out2 = p.out2[head];
-      for (int n = tid >> 7; n < n_out; n += 2) {
-        const float raw = red[n * HP_PX + px] + red[(32 + n) * HP_PX + px] + red[(64 + n) * HP_PX + px] +
-                          red[(96 + n) * HP_PX + px] + bo[n];
-        const size_t o = ((size_t)b * n_out + n) * p.HW + (size_t)y * q.W + x;
-        float v = raw;
-        if (act == CF_ACT_RELU) v = fmaxf(raw, 0.0f);
-        else if (act == CF_ACT_SIGMOID_CLAMP) v = fminf(fmaxf(cf_sigmoid(raw), 1e-4f), 1.0f - 1e-4f);
-        out[o] = v;
-        if (act == CF_ACT_RAW_AND_SIGDEPTH) out2[o] = 1.0f / (cf_sigmoid(raw) + 1e-6f) - 1.0f;
-      }
-    }
-  }
-}
-
-
-#endif  // CF_LEGACY_HEADS
-
-// ---------------------------------------------------------------------------------------------
-// The same whole-head patch kernel on v_mfma_f32_16x16x32_bf16.  Under the chip's power management a dense MFMA
-// loop on random data holds a higher clock with the 16x16x32 shape than with 32x32x16 at equal cycles per FLOP:
-// measured on this part 1.72 vs 1.51 PFLOP/s with every operand re-read from LDS (tools/micro/mfma_shape.hip,
-// MI355X_MICROARCH.md "DVFS give-back" item 7) - and this kernel is bound by exactly that loop.  Same tile (8 x 16
-// pixels), same LDS patch, same operand bytes per FLOP: a wave owns 64 hidden channels x 128 pixels as 4 x 8
-// accumulators of 16 x 16; a k-step is 32 deep = half the channels of one tap (or four taps of the 8-channel pc_hm
-// plane pair).  Weights come as [16-row tile][k32 step][hi|lo][lane][8] fragments (packing.pack_fragments16), one
-// k-step ahead in registers.  The 256 -> n_out layer again runs from the accumulator registers: two stacked 16 x 16
-// tiles give a lane 4 + 4 channels of one pixel = one B fragment, with w_out packed in that k order
-// (pack_fragments16(acc_order=True)); n_out <= 16.
-// ---------------------------------------------------------------------------------------------
-//
 // MX = true: the FIRST layer on "fp16 main term + block-scaled FP6 cross terms" (1.5 MFMA passes per product instead of the 3
 // of bf16x3; numerics and the gate that confines the scheme to the first layer: packing.pack_head_first_mx).  The
 // feature source is the 272-byte-per-pixel image cf_pack_feat_mx writes - four 64-byte segments g = 0..3, each [8 fp16: channels
@@ -1210,7 +589,7 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
     f32x4 acc[4][8];
     first_layer(head, acc);
     // hidden layers need all 256 channels of a pixel: the two 64-pixel halves of the tile go through
-    // the LDS-resident chain of cf_head_tail one after the other (LDS stays at 66 KiB: 2 workgroups/CU)
+    // the LDS-resident chain (head_tail_from_lds16) one after the other (LDS stays at 66 KiB: 2 workgroups/CU)
     __syncthreads();                         // every wave is done with the patch
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
@@ -1357,14 +736,13 @@ extern "C" int cf_pack_feat_mx(const float* x, int in_stride, void* rows, long M
   return cf_pack_feat_mx_scaled(x, in_stride, rows, M, 16.0f, stream);
 }
 
-static int fill_tail(const cf_head_tail_args* a, HeadTailK& k, const char* who, bool need_x) {
-  CF_REQUIRE(a != nullptr, "%s: null args", who);
-  CF_REQUIRE(!need_x || (a->x && a->x_stride >= 256 && a->x_stride % 8 == 0), "%s: bad input tensor", who);
-  CF_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0, "%s: bad geometry", who);
-  CF_REQUIRE(a->n_heads >= 1 && a->n_heads <= CF_MAX_HEADS, "%s: n_heads=%d", who, a->n_heads);
-  CF_REQUIRE(a->n_hidden >= 0 && a->n_hidden <= 2, "%s: n_hidden=%d", who, a->n_hidden);
+// the tail member of the argument block -> kernel arguments (tail.x / x_stride / c_base are not read: the hidden tile is born in LDS)
+static int fill_tail(const cf_head_tail_args* a, HeadTailK& k) {
+  CF_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0, "cf_head_fused: bad geometry");
+  CF_REQUIRE(a->n_heads >= 1 && a->n_heads <= CF_MAX_HEADS, "cf_head_fused: n_heads=%d", a->n_heads);
+  CF_REQUIRE(a->n_hidden >= 0 && a->n_hidden <= 2, "cf_head_fused: n_hidden=%d", a->n_hidden);
   const long M = (long)a->B * a->H * a->W;
-  CF_REQUIRE(M < (1L << 31), "%s: tensor too large", who);
+  CF_REQUIRE(M < (1L << 31), "cf_head_fused: tensor too large");
   k.x = reinterpret_cast<const unsigned char*>(a->x);
   k.x_stride = a->x_stride;
   k.M = (int)M;
@@ -1373,15 +751,13 @@ static int fill_tail(const cf_head_tail_args* a, HeadTailK& k, const char* who, 
   k.n_hidden = a->n_hidden;
   for (int i = 0; i < a->n_heads; ++i) {
     for (int l = 0; l < a->n_hidden; ++l) {
-      CF_REQUIRE(a->w_hidden[i][l] && a->b_hidden[i][l], "%s: head %d layer %d weights missing", who, i, l);
+      CF_REQUIRE(a->w_hidden[i][l] && a->b_hidden[i][l], "cf_head_fused: head %d layer %d weights missing", i, l);
       k.w_hidden[i][l] = reinterpret_cast<const unsigned char*>(a->w_hidden[i][l]);
       k.b_hidden[i][l] = a->b_hidden[i][l];
     }
-    CF_REQUIRE(a->w_out[i] && a->b_out[i] && a->out[i], "%s: head %d output layer missing", who, i);
-    CF_REQUIRE(a->n_out[i] >= 1 && a->n_out[i] <= 32, "%s: head %d n_out=%d", who, i, a->n_out[i]);
-    CF_REQUIRE(!need_x || (a->c_base[i] >= 0 && a->c_base[i] % 8 == 0 && a->c_base[i] + 256 <= a->x_stride),
-               "%s: head %d channel slice out of range", who, i);
-    CF_REQUIRE(a->act[i] != CF_ACT_RAW_AND_SIGDEPTH || a->out2[i], "%s: head %d needs out2", who, i);
+    CF_REQUIRE(a->w_out[i] && a->b_out[i] && a->out[i], "cf_head_fused: head %d output layer missing", i);
+    CF_REQUIRE(a->n_out[i] >= 1 && a->n_out[i] <= 32, "cf_head_fused: head %d n_out=%d", i, a->n_out[i]);
+    CF_REQUIRE(a->act[i] != CF_ACT_RAW_AND_SIGDEPTH || a->out2[i], "cf_head_fused: head %d needs out2", i);
     k.w_out[i] = reinterpret_cast<const unsigned char*>(a->w_out[i]);
     k.b_out[i] = a->b_out[i];
     k.out[i] = a->out[i];
@@ -1393,191 +769,122 @@ static int fill_tail(const cf_head_tail_args* a, HeadTailK& k, const char* who, 
   return CF_OK;
 }
 
-// Kernels of rounds 1-3 that no default or switchable path of the host dispatches any more - the stand-alone tail
-// (cf_head_tail), the slot-table fused head and the 32x32x16 patch kernel (cf_head_fused without mfma16 / layout3x3) - are
-// compiled only with -DCF_LEGACY_HEADS (build.py never sets it): the default library answers those calls with CF_EINVAL.
-#ifndef CF_LEGACY_HEADS
-#define CF_LEGACY_ONLY(what) CF_REQUIRE(false, "%s is a legacy kernel path: rebuild libcfhip with -DCF_LEGACY_HEADS (CF_EXTRA_FLAGS), " \
-                                               "or pack the heads for the 16x16x32 patch kernel (mfma16 = 1, layout3x3 = 1, n_out <= 16)", what)
-#endif
-
-extern "C" int cf_head_tail(const cf_head_tail_args* a, void* stream) {
-  HeadTailK k{};
-  const int rc = fill_tail(a, k, "cf_head_tail", true);
-  if (rc != CF_OK) return rc;
-#ifdef CF_LEGACY_HEADS
-  static CfLdsLimit lds_limit;
-  lds_limit.ensure(head_tail_kernel, HT_LDS, HT_LDS);
-  const int tiles = (k.M + HT_PX - 1) / HT_PX;
-  hipLaunchKernelGGL(head_tail_kernel, dim3(tiles * a->n_heads), dim3(256), HT_LDS, (hipStream_t)stream, k);
-  return cf_check_launch("cf_head_tail");
-#else
-  (void)stream;
-  CF_LEGACY_ONLY("cf_head_tail");
-  return CF_EINVAL;
-#endif
-}
+// The one form that runs: the canonical 3x3 slot order (layout3x3 = 1) over a 64-channel first source [and an 8-channel
+// pc_hm source] with every weight packed as 16x16x32 fragments (mfma16 = 1).  The argument block can still spell the
+// forms of the earlier kernels (32x32x16 fragments, an arbitrary slot table): those are refused, never reinterpreted.
+constexpr int HEAD_MAX_K_PAD = 2048;   // bound of cf_head_fused_args.K_pad (64 chunks of 32)
+#define CF_HEAD_FORMS "cf_head_fused runs layout3x3 = 1 (64-channel first source [, 8-channel second]) with mfma16 = 1 " \
+                      "(16x16x32 fragments, n_out <= 16) only"
 
 extern "C" int cf_head_fused(const cf_head_fused_args* a, void* stream) {
   CF_REQUIRE(a != nullptr, "cf_head_fused: null args");
-  HeadFusedK k{};
-  const int rc = fill_tail(&a->tail, k.t, "cf_head_fused", false);
+  HeadPatchK hp{};
+  const int rc = fill_tail(&a->tail, hp.t);
   if (rc != CF_OK) return rc;
   CF_REQUIRE(a->n_src >= 1 && a->n_src <= 2, "cf_head_fused: n_src=%d", a->n_src);
   for (int i = 0; i < a->n_src; ++i) {
     CF_REQUIRE(a->src[i] && a->src_c[i] > 0 && a->src_c[i] % 8 == 0, "cf_head_fused: source %d invalid", i);
-    k.src[i] = reinterpret_cast<const unsigned char*>(a->src[i]);
-    k.src_c[i] = a->src_c[i];
+    hp.src[i] = reinterpret_cast<const unsigned char*>(a->src[i]);
+    hp.src_c[i] = a->src_c[i];
   }
-  if (a->mx) {                             // the mx operand stream has no slot table: only the 3x3 patch kernel reads it
+  const bool mx = a->mx != 0;                // first layer: fp16 main + FP6 cross terms on the mx feature rows
+  if (mx) {                                  // the mx operand stream has no slot table
     CF_REQUIRE(a->layout3x3 && a->mfma16 && a->src_c[0] == 64 && (a->n_src == 1 || a->src_c[1] == 8),
                "cf_head_fused: mx = 1 needs layout3x3 = 1, mfma16 = 1, a 64-channel mx source [and an 8-channel pc_hm source]");
   } else {
     CF_REQUIRE(a->slots && a->K_pad > 0 && a->K_pad % 64 == 0, "cf_head_fused: K_pad=%d must be a multiple of 64", a->K_pad);
-    CF_REQUIRE(a->K_pad / 32 <= HF_MAX_CHUNKS, "cf_head_fused: K_pad=%d exceeds %d", a->K_pad, HF_MAX_CHUNKS * 32);
+    CF_REQUIRE(a->K_pad <= HEAD_MAX_K_PAD, "cf_head_fused: K_pad=%d exceeds %d", a->K_pad, HEAD_MAX_K_PAD);
   }
-  k.slots = a->slots;
-  k.n_chunks = a->K_pad / 32;
-  k.H = a->tail.H;
-  k.W = a->tail.W;
-  for (int i = 0; i < a->tail.n_heads; ++i) {
+  const int n_heads = a->tail.n_heads, H = a->tail.H, W = a->tail.W;
+  for (int i = 0; i < n_heads; ++i) {
     CF_REQUIRE(a->w_first[i] && a->b_first[i], "cf_head_fused: head %d first layer missing", i);
-    k.w_first[i] = reinterpret_cast<const unsigned char*>(a->w_first[i]);
-    k.b_first[i] = a->b_first[i];
+    hp.w_first[i] = reinterpret_cast<const unsigned char*>(a->w_first[i]);
+    hp.b_first[i] = a->b_first[i];
   }
-  if (a->layout3x3 && a->src_c[0] == 64 && (a->n_src == 1 || a->src_c[1] == 8)) {
-    // 2-D patch kernel: K order = 9 taps x 64 feature channels [, then the pc_hm taps pairwise]
-    HeadPatchK hp{};
-    hp.t = k.t;
-    hp.src[0] = k.src[0]; hp.src[1] = k.src[1];
-    hp.src_c[0] = k.src_c[0]; hp.src_c[1] = k.src_c[1];
-    hp.H = k.H; hp.W = k.W;
-    hp.tiles_x = (k.W + HP_TW - 1) / HP_TW;
-    hp.tiles_y = (k.H + HP_TH - 1) / HP_TH;
-    const bool m16 = a->mfma16 != 0;         // fragments packed for v_mfma_f32_16x16x32_bf16 (k-steps of 32)
-    const bool mx = a->mx != 0;              // first layer: fp16 main + FP6 cross terms on the mx feature rows
-    CF_REQUIRE(!mx || m16, "cf_head_fused: mx = 1 needs mfma16 = 1 (the tail layers run on 16x16x32 fragments)");
-    hp.n_ks = m16 ? a->K_pad / 32 : a->K_pad / 16;
-    CF_REQUIRE(mx || a->K_pad / 16 >= (a->n_src == 2 ? 41 : 36), "cf_head_fused: K_pad=%d too small for the 3x3 layout", a->K_pad);
-    for (int i = 0; i < a->tail.n_heads; ++i) {
-      CF_REQUIRE(!mx || (a->first_scale[i] > 0.0f && a->first_scale[i] < 1e30f), "cf_head_fused: head %d: first_scale missing (mx)", i);
-      hp.first_scale[i] = a->first_scale[i];
-    }
-    if (m16) {
-      CF_REQUIRE(mx || (a->K_pad % 32 == 0 && a->K_pad / 32 >= (a->n_src == 2 ? 21 : 18)), "cf_head_fused: K_pad=%d (16x16x32 fragments)", a->K_pad);
-      for (int i = 0; i < a->tail.n_heads; ++i)
-        CF_REQUIRE(a->tail.n_out[i] <= 16, "cf_head_fused: head %d: n_out=%d > 16 (the 16x16x32 kernels produce ONE 16-row output tile, with or without hidden layers)", i, a->tail.n_out[i]);
-    }
-    for (int i = 0; i < a->tail.n_heads; ++i) {
-      CF_REQUIRE(a->tail.n_hidden > 0 || a->w_out_perm[i], "cf_head_fused: head %d: w_out_perm missing", i);
-      hp.w_first[i] = k.w_first[i];
-      hp.b_first[i] = k.b_first[i];
-      hp.w_out_perm[i] = reinterpret_cast<const unsigned char*>(a->w_out_perm[i]);
-    }
-    {
-      // grid order: head-major (0).  Measured alternatives (CF_HEAD_GROUP = g, dev tools only): tile-major over all heads
-      // of the launch takes the same time but 2.2x the fabric fetches - the 7 heads' first-layer weights (4.1 MB) no
-      // longer fit an XCD's 4 MB L2 next to the patches; groups of 2 or 4 heads run 3-4 % slower
-      const char* e = getenv("CF_HEAD_GROUP");
-      hp.group = e ? atoi(e) : 0;
-      if (hp.group < 0 || hp.group > a->tail.n_heads) hp.group = 0;
-    }
-    const int n_groups = hp.group ? (a->tail.n_heads + hp.group - 1) / hp.group : 1;
-    const long blocks = (long)hp.tiles_x * hp.tiles_y * a->tail.B * (hp.group ? (long)n_groups * hp.group : a->tail.n_heads);
-    CF_REQUIRE(blocks < (1L << 31), "cf_head_fused: grid too large");
-#ifdef CF_LEGACY_HEADS
-    static CfLdsLimit lim_plain, lim_pc;
-    lim_plain.ensure(head_patch_kernel<4, false>, HP_LDS, HP_LDS);
-    lim_pc.ensure(head_patch_kernel<4, true>, HP_LDS, HP_LDS);
-#endif
-    if (m16) {
-      // heads without hidden layers: a workgroup walks several heads on one patch (chosen below; CF_HEAD_LOOP overrides
-      // for dev tools).  With hidden layers the chain rewrites the patch: one head per workgroup.
-      int hloop = 1;
-      // tile orientation: 8 x 16 or 16 x 8 pixels, whichever covers the map with fewer tiles (results do not depend on it;
-      // CF_HEAD_TILE = 0 / 1 forces one for dev tools)
-      const long t_land = (long)((k.W + 15) / 16) * ((k.H + 7) / 8), t_port = (long)((k.W + 7) / 8) * ((k.H + 15) / 16);
-      bool portrait = t_port < t_land;
-      if (const char* e = getenv("CF_HEAD_TILE")) portrait = atoi(e) != 0;
-      if (portrait) {
-        hp.tiles_x = (k.W + 7) / 8;
-        hp.tiles_y = (k.H + 15) / 16;
-      }
-      if (a->tail.n_hidden == 0) {
-        // heads per workgroup: 1, 2 or half of them, whichever needs the fewest rounds of (2 workgroups per CU) x (heads +
-        // a quarter of a head's time for the patch) - small batches want many short workgroups (bs=1: 103 vs 123 us with
-        // 1 vs 4 heads), bs=16 the long ones (1307 vs 1331 us).  The results do not depend on it.
-        static const int slots = [] {
-          int dev = 0, cus = 256;
-          if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-          return 2 * (cus > 0 ? cus : 256);
-        }();
-        const long tiles = (long)hp.tiles_x * hp.tiles_y * a->tail.B;
-        const int n = a->tail.n_heads, cand[3] = {1, 2, (n + 1) / 2};
-        double best = 0.0;
-        for (int i = 0; i < 3; ++i) {
-          const int h = cand[i] < 1 ? 1 : (cand[i] > n ? n : cand[i]);
-          const double cost = (double)((tiles * ((n + h - 1) / h) + slots - 1) / slots) * (h + 0.25);
-          if (i == 0 || cost < best - 1e-9) { best = cost; hloop = h; }
-        }
-        if (const char* e = getenv("CF_HEAD_LOOP")) hloop = atoi(e);
-        if (hloop < 1) hloop = 1;
-        if (hloop > n) hloop = n;
-      }
-      hp.hloop = hloop;
-      const long blocks16 = (long)hp.tiles_x * hp.tiles_y * a->tail.B * ((a->tail.n_heads + hloop - 1) / hloop);
-      const bool hidden = a->tail.n_hidden > 0;
-      const bool pc = a->n_src == 2;
-      const int lds = hp16_lds(pc, hidden);
-      auto launch = [&](auto kernel, CfLdsLimit& lim) {
-        lim.ensure(kernel, lds, hp16_lds(pc, false));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks16), dim3(256), lds, (hipStream_t)stream, hp);
-      };
-      static CfLdsLimit lim16[4], limx[4];
-      if (mx) {
-        static CfLdsLimit limxh[2];
-        if (hidden) {
-          // (hidden layers behind an mx first layer WITHOUT the pc_hm source: that instantiation does not fit 256 registers
-          //  without scratch, and no configuration of the reference has such heads - its packing stays bf16x3)
-          CF_REQUIRE(pc, "cf_head_fused: mx = 1 with hidden layers needs the pc_hm source (n_src = 2); pack such heads for bf16x3");
-          if (portrait) launch(head_patch16_kernel<4, true, true, true, 1>, limxh[1]);
-          else launch(head_patch16_kernel<4, true, false, true, 1>, limxh[0]);
-        } else {
-          if (pc && portrait) launch(head_patch16_kernel<4, true, true, true, 0>, limx[3]);
-          else if (pc) launch(head_patch16_kernel<4, true, false, true, 0>, limx[2]);
-          else if (portrait) launch(head_patch16_kernel<4, false, true, true, 0>, limx[1]);
-          else launch(head_patch16_kernel<4, false, false, true, 0>, limx[0]);
-        }
-        return cf_check_launch("cf_head_fused");
-      }
-      if (pc && portrait) launch(head_patch16_kernel<4, true, true>, lim16[3]);
-      else if (pc) launch(head_patch16_kernel<4, true, false>, lim16[2]);
-      else if (portrait) launch(head_patch16_kernel<4, false, true>, lim16[1]);
-      else launch(head_patch16_kernel<4, false, false>, lim16[0]);
-      return cf_check_launch("cf_head_fused");
-    }
-#ifdef CF_LEGACY_HEADS
-    if (a->n_src == 2)
-      hipLaunchKernelGGL((head_patch_kernel<4, true>), dim3((unsigned)blocks), dim3(256), HP_LDS, (hipStream_t)stream, hp);
-    else
-      hipLaunchKernelGGL((head_patch_kernel<4, false>), dim3((unsigned)blocks), dim3(256), HP_LDS, (hipStream_t)stream, hp);
-    return cf_check_launch("cf_head_fused");
-#else
-    (void)blocks;
-    CF_LEGACY_ONLY("cf_head_fused with 32x32x16 fragments (mfma16 = 0)");
-#endif
+  if (!(a->layout3x3 && a->src_c[0] == 64 && (a->n_src == 1 || a->src_c[1] == 8))) {
+    // nothing but the 3x3 patch kernel reads 16x16x32 fragments
+    CF_REQUIRE(a->mfma16 == 0, "cf_head_fused: mfma16 fragments need the 3x3 patch layout (layout3x3 = 1, 64-channel first "
+                               "source [, 8-channel second]); this launch would run on the 32x32x16 slot-table kernel");
+    cf_set_error(CF_HEAD_FORMS ": there is no slot-table kernel (layout3x3 = 0)");
+    return CF_EINVAL;
   }
-  // the slot-table kernel reads every weight as 32x32x16 fragments: 16x16x32-packed ones would be misread silently
-  CF_REQUIRE(a->mfma16 == 0, "cf_head_fused: mfma16 fragments need the 3x3 patch layout (layout3x3 = 1, 64-channel first "
-                             "source [, 8-channel second]); this launch would run on the 32x32x16 slot-table kernel");
-#ifdef CF_LEGACY_HEADS
-  static CfLdsLimit lds_limit;
-  lds_limit.ensure(head_fused_kernel, HF_LDS, HF_LDS);
-  const int tiles = (k.t.M + HT_PX - 1) / HT_PX;
-  hipLaunchKernelGGL(head_fused_kernel, dim3(tiles * a->tail.n_heads), dim3(256), HF_LDS, (hipStream_t)stream, k);
+  // K order = 9 taps x 64 feature channels [, then the pc_hm taps four at a time]
+  const bool m16 = a->mfma16 != 0;           // fragments packed for v_mfma_f32_16x16x32_bf16 (k-steps of 32)
+  hp.H = H; hp.W = W;
+  hp.n_ks = a->K_pad / 32;
+  CF_REQUIRE(mx || a->K_pad / 16 >= (a->n_src == 2 ? 41 : 36), "cf_head_fused: K_pad=%d too small for the 3x3 layout", a->K_pad);
+  for (int i = 0; i < n_heads; ++i) {
+    CF_REQUIRE(!mx || (a->first_scale[i] > 0.0f && a->first_scale[i] < 1e30f), "cf_head_fused: head %d: first_scale missing (mx)", i);
+    hp.first_scale[i] = a->first_scale[i];
+  }
+  if (m16) {
+    CF_REQUIRE(mx || (a->K_pad % 32 == 0 && a->K_pad / 32 >= (a->n_src == 2 ? 21 : 18)), "cf_head_fused: K_pad=%d (16x16x32 fragments)", a->K_pad);
+    for (int i = 0; i < n_heads; ++i)
+      CF_REQUIRE(a->tail.n_out[i] <= 16, "cf_head_fused: head %d: n_out=%d > 16 (the 16x16x32 kernels produce ONE 16-row output tile, with or without hidden layers)", i, a->tail.n_out[i]);
+  }
+  for (int i = 0; i < n_heads; ++i) {
+    CF_REQUIRE(a->tail.n_hidden > 0 || a->w_out_perm[i], "cf_head_fused: head %d: w_out_perm missing", i);
+    hp.w_out_perm[i] = reinterpret_cast<const unsigned char*>(a->w_out_perm[i]);
+  }
+  // tile orientation: 8 x 16 or 16 x 8 pixels, whichever covers the map with fewer tiles (results do not depend on it;
+  // CF_HEAD_TILE = 0 / 1 forces one for dev tools)
+  const long t_land = (long)((W + 15) / 16) * ((H + 7) / 8), t_port = (long)((W + 7) / 8) * ((H + 15) / 16);
+  CF_REQUIRE(t_land * a->tail.B * n_heads < (1L << 31), "cf_head_fused: grid too large");   // (bounds either orientation's grid)
+  CF_REQUIRE(m16, CF_HEAD_FORMS ": nothing reads 32x32x16 fragments (mfma16 = 0)");
+  bool portrait = t_port < t_land;
+  if (const char* e = getenv("CF_HEAD_TILE")) portrait = atoi(e) != 0;
+  hp.tiles_x = portrait ? (W + 7) / 8 : (W + 15) / 16;
+  hp.tiles_y = portrait ? (H + 15) / 16 : (H + 7) / 8;
+  // heads without hidden layers: a workgroup walks several heads on one patch (chosen below; CF_HEAD_LOOP overrides
+  // for dev tools).  With hidden layers the chain rewrites the patch: one head per workgroup.
+  int hloop = 1;
+  if (a->tail.n_hidden == 0) {
+    // heads per workgroup: 1, 2 or half of them, whichever needs the fewest rounds of (2 workgroups per CU) x (heads +
+    // a quarter of a head's time for the patch) - small batches want many short workgroups (bs=1: 103 vs 123 us with
+    // 1 vs 4 heads), bs=16 the long ones (1307 vs 1331 us).  The results do not depend on it.
+    static const int slots = [] {
+      int dev = 0, cus = 256;
+      if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+      return 2 * (cus > 0 ? cus : 256);
+    }();
+    const long tiles = (long)hp.tiles_x * hp.tiles_y * a->tail.B;
+    const int n = n_heads, cand[3] = {1, 2, (n + 1) / 2};
+    double best = 0.0;
+    for (int i = 0; i < 3; ++i) {
+      const int h = cand[i] < 1 ? 1 : (cand[i] > n ? n : cand[i]);
+      const double cost = (double)((tiles * ((n + h - 1) / h) + slots - 1) / slots) * (h + 0.25);
+      if (i == 0 || cost < best - 1e-9) { best = cost; hloop = h; }
+    }
+    if (const char* e = getenv("CF_HEAD_LOOP")) hloop = atoi(e);
+    if (hloop < 1) hloop = 1;
+    if (hloop > n) hloop = n;
+  }
+  hp.hloop = hloop;
+  const long blocks = (long)hp.tiles_x * hp.tiles_y * a->tail.B * ((n_heads + hloop - 1) / hloop);
+  const bool hidden = a->tail.n_hidden > 0;
+  const bool pc = a->n_src == 2;
+  const int lds = hp16_lds(pc, hidden);
+  auto launch = [&](auto kernel, CfLdsLimit& lim) {
+    lim.ensure(kernel, lds, hp16_lds(pc, false));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, hp);
+  };
+  static CfLdsLimit lim16[4], limx[4], limxh[2];
+  if (mx && hidden) {
+    // (hidden layers behind an mx first layer WITHOUT the pc_hm source: that instantiation does not fit 256 registers
+    //  without scratch, and no configuration of the reference has such heads - its packing stays bf16x3)
+    CF_REQUIRE(pc, "cf_head_fused: mx = 1 with hidden layers needs the pc_hm source (n_src = 2); pack such heads for bf16x3");
+    if (portrait) launch(head_patch16_kernel<4, true, true, true, 1>, limxh[1]);
+    else launch(head_patch16_kernel<4, true, false, true, 1>, limxh[0]);
+  } else if (mx) {
+    if (pc && portrait) launch(head_patch16_kernel<4, true, true, true, 0>, limx[3]);
+    else if (pc) launch(head_patch16_kernel<4, true, false, true, 0>, limx[2]);
+    else if (portrait) launch(head_patch16_kernel<4, false, true, true, 0>, limx[1]);
+    else launch(head_patch16_kernel<4, false, false, true, 0>, limx[0]);
+  } else {
+    if (pc && portrait) launch(head_patch16_kernel<4, true, true>, lim16[3]);
+    else if (pc) launch(head_patch16_kernel<4, true, false>, lim16[2]);
+    else if (portrait) launch(head_patch16_kernel<4, false, true>, lim16[1]);
+    else launch(head_patch16_kernel<4, false, false>, lim16[0]);
+  }
   return cf_check_launch("cf_head_fused");
-#else
-  CF_LEGACY_ONLY("cf_head_fused on the slot-table kernel (layout3x3 = 0)");
-  return CF_EINVAL;
-#endif
 }

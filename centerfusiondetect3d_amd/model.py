@@ -23,8 +23,7 @@ import torch
 from torch import nn
 
 from . import _lib, ops, packing
-from ._lib import (ACT_NONE, ACT_RELU, ACT_SIGMOID_CLAMP, ACT_RAW_AND_SIGDEPTH, LAYOUT_NHWC,
-                   LAYOUT_NCHW, LAYOUT_NHWC_SPLIT_BF16)
+from ._lib import (ACT_NONE, ACT_RELU, ACT_SIGMOID_CLAMP, ACT_RAW_AND_SIGDEPTH, LAYOUT_NHWC, LAYOUT_NCHW)
 from .packing import Source
 
 SECONDARY_HEADS = ["velocity", "nuscenes_att", "depth2", "rotation2"]   # detectHeads.py:146-153
@@ -1067,40 +1066,43 @@ class DLASeg(nn.Module):
             if any(c != 256 for c in head_conv[h]):
                 raise NotImplementedError("head_conv widths other than 256 are not on the path")
         bf = self._heads_bf()
-        pack = packing.pack_conv_bf16 if bf else packing.pack_conv
         feat_src = Source(64, 64)
         pc_src = Source(3, 8 if bf else 4)
         hw = lambda h, i: sd[f"{hp}.{h}.{i}.weight"].float().cpu()
         hb = lambda h, i: sd[f"{hp}.{h}.{i}.bias"].float().cpu()
-        pk["heads.primary.0"] = pack(torch.cat([hw(h, 0) for h in primary], 0),
-                                     torch.cat([hb(h, 0) for h in primary], 0), [feat_src]).to(device)
-        for n, h in enumerate(primary):
+        for h in primary:
             assert len(head_conv[h]) == 1
-            pk[f"heads.{h}.out"] = pack(hw(h, 2), hb(h, 2), [Source(256, 256 * len(primary), 256 * n)]).to(device)
-        if radar:
-            pk["heads.secondary.0"] = pack(torch.cat([hw(h, 0) for h in SECONDARY_HEADS], 0),
-                                           torch.cat([hb(h, 0) for h in SECONDARY_HEADS], 0),
-                                           [feat_src, pc_src]).to(device)
-            ns = 256 * len(SECONDARY_HEADS)
-            for n, h in enumerate(SECONDARY_HEADS):
-                assert len(head_conv[h]) == 3
-                for idx in (2, 4):
-                    pk[f"heads.{h}.{idx}"] = pack(hw(h, idx), hb(h, idx), [Source(256, ns, 256 * n)]).to(device)
-                pk[f"heads.{h}.out"] = pack(hw(h, 6), hb(h, 6), [Source(256, ns, 256 * n)]).to(device)
-        if bf:
-            m16 = True               # 16x16x32 fragments: what head_patch16_kernel reads (_heads_bf: every head has <= 16 outputs)
+        for h in (SECONDARY_HEADS if radar else ()):
+            assert len(head_conv[h]) == 3
+        if not bf:
+            # the exact-fp32 layer-by-layer heads (cf_conv2d_fused); the fused launches below read none of these
+            pack = packing.pack_conv
+            pk["heads.primary.0"] = pack(torch.cat([hw(h, 0) for h in primary], 0),
+                                         torch.cat([hb(h, 0) for h in primary], 0), [feat_src]).to(device)
+            for n, h in enumerate(primary):
+                pk[f"heads.{h}.out"] = pack(hw(h, 2), hb(h, 2), [Source(256, 256 * len(primary), 256 * n)]).to(device)
+            if radar:
+                pk["heads.secondary.0"] = pack(torch.cat([hw(h, 0) for h in SECONDARY_HEADS], 0),
+                                               torch.cat([hb(h, 0) for h in SECONDARY_HEADS], 0),
+                                               [feat_src, pc_src]).to(device)
+                ns = 256 * len(SECONDARY_HEADS)
+                for n, h in enumerate(SECONDARY_HEADS):
+                    for idx in (2, 4):
+                        pk[f"heads.{h}.{idx}"] = pack(hw(h, idx), hb(h, idx), [Source(256, ns, 256 * n)]).to(device)
+                    pk[f"heads.{h}.out"] = pack(hw(h, 6), hb(h, 6), [Source(256, ns, 256 * n)]).to(device)
+        else:
+            # 16x16x32 fragments: what head_patch16_kernel reads (_heads_bf: every head has <= 16 outputs)
+            pf = packing.pack_fragments16
             def tail(h, hidden_idx, out_idx):
                 n_out = heads[h]
                 b32 = torch.zeros(32)
                 b32[:n_out] = hb(h, out_idx)
                 w2 = hw(h, out_idx).view(n_out, 256)
-                perm = (packing.pack_fragments16(w2, acc_order=True) if m16 else packing.pack_fragments(w2, acc_order=True))
-                pf = packing.pack_fragments16 if m16 else packing.pack_fragments
                 return dict(w_hidden=[pf(hw(h, i).view(256, 256)).to(device) for i in hidden_idx],
                             b_hidden=[hb(h, i).to(device) for i in hidden_idx],
-                            w_out=pf(w2).to(device), w_out_perm=perm.to(device),
-                            b_out=b32.to(device), n_out=n_out, mfma16=m16)
-            mx = m16 and bool(self.heads_mx)
+                            w_out=pf(w2).to(device), w_out_perm=pf(w2, acc_order=True).to(device),
+                            b_out=b32.to(device), n_out=n_out, mfma16=True)
+            mx = bool(self.heads_mx)
             self._mx_active = mx
             # the mx rows' pre-scale: one for both head groups (they read the same rows)
             fr = [self._ranges[n] for n in ("heads.primary.0", "heads.secondary.0") if self._ranges and n in self._ranges]
@@ -1110,7 +1112,7 @@ class DLASeg(nn.Module):
                     d = packing.pack_head_first_mx(hw(h, 0), hb(h, 0), pc=len(srcs) == 2, feat_scale=self._feat_scale)
                     return dict(w_first=d["w_first"].to(device), b_first=d["b_first"].to(device), first_scale=d["first_scale"],
                                 real_cin=d["real_cin"])
-                pc = packing.pack_conv_bf16(hw(h, 0), hb(h, 0), srcs, fragments=16 if m16 else True).to(device)
+                pc = packing.pack_conv_bf16(hw(h, 0), hb(h, 0), srcs).to(device)
                 return dict(w_first=pc.weight, b_first=pc.bias[:256].contiguous(), slots=pc.slots, k_pad=pc.k_pad,
                             real_cin=pc.real_cin)
             pk["tails.primary"] = {h: dict(tail(h, [], 2), **first(h, [feat_src])) for h in primary}

@@ -10,8 +10,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import (ACT_NONE, ACT_RELU, ACT_SIGMOID_CLAMP, ACT_RAW_AND_SIGDEPTH, LAYOUT_NHWC,
-                   LAYOUT_NCHW, LAYOUT_NHWC_SPLIT_BF16)
+from ._lib import (ACT_NONE, ACT_RELU, ACT_SIGMOID_CLAMP, ACT_RAW_AND_SIGDEPTH, LAYOUT_NHWC, LAYOUT_NCHW)
 from .packing import PackedConv, PackedDcn, MX_ROW as packing_MX_ROW
 
 
@@ -163,10 +162,6 @@ def conv2d_fused(pc: PackedConv, srcs, B, H, W, act=ACT_NONE, residual=None, lay
     return (out, out2) if act == ACT_RAW_AND_SIGDEPTH else out
 
 
-def run_conv_bf16(a: _lib.ConvArgs):
-    _lib.check(_lib.load().cf_conv2d_bf16x3(C.byref(a), _lib.stream_ptr()), "cf_conv2d_bf16x3")
-
-
 def split_bf16(x, channels=None, cs=None, out=None):
     """fp32 NHWC (B,H,W,S) -> split-bf16 (B,H,W,2,Cs) stored as a bf16 tensor."""
     _need_cuda(x)
@@ -180,28 +175,9 @@ def split_bf16(x, channels=None, cs=None, out=None):
     return out
 
 
-def conv2d_bf16x3(pc: PackedConv, srcs, B, H, W, act=ACT_NONE, layout=LAYOUT_NHWC_SPLIT_BF16,
-                  out=None, out2=None):
-    """srcs: split-bf16 tensors (B,H,W,2,Cs).  Returns split-bf16 (B,Ho,Wo,2,N) or fp32 NCHW."""
-    _need_cuda(*srcs)
-    Ho = (H + 2 * pc.pad - pc.kh) // pc.stride + 1
-    Wo = (W + 2 * pc.pad - pc.kh) // pc.stride + 1
-    dev = srcs[0].device
-    if out is None:
-        if layout == LAYOUT_NHWC_SPLIT_BF16:
-            out = torch.empty((B, Ho, Wo, 2, pc.n), device=dev, dtype=torch.bfloat16)
-        else:
-            out = torch.empty((B, pc.n, Ho, Wo), device=dev, dtype=torch.float32)
-    if act == ACT_RAW_AND_SIGDEPTH and out2 is None:
-        out2 = torch.empty_like(out)
-    a = conv_args(pc, srcs, [s.shape[-1] for s in srcs], B, H, W, out, pc.n, act, None, 0, layout,
-                  out2, 0, False)
-    run_conv_bf16(a)
-    return (out, out2) if act == ACT_RAW_AND_SIGDEPTH else out
-
-
 def head_tail_args(x, x_stride, B, H, W, heads):
-    """heads: list of dicts {c_base, w_hidden:[frag tensors], b_hidden:[f32 tensors], w_out, b_out,
+    """The `tail` member of cf_head_fused's argument block (head_fused_args builds the whole block; x / x_stride / c_base are
+    not read by the launch).  heads: list of dicts {c_base, w_hidden:[frag tensors], b_hidden:[f32 tensors], w_out, b_out,
     n_out, act, out (NCHW tensor or None), out2}.  Outputs may be patched later (a.out[i] = ptr)."""
     a = _lib.HeadTailArgs()
     a.x, a.x_stride, a.B, a.H, a.W = x.data_ptr(), x_stride, B, H, W
@@ -219,9 +195,10 @@ def head_tail_args(x, x_stride, B, H, W, heads):
 
 
 def head_fused_args(srcs, src_strides, slots, k_pad, B, H, W, heads, layout3x3=None):
-    """heads: as head_tail_args plus w_first (fragment-packed [8][K_pad/16]...) and b_first (256 f32).
-    layout3x3 (default: every head carries w_out_perm): the slots are pack_conv_bf16's canonical order for
-    [feat 64 (, pc_hm 8)] sources, so the 2-D patch kernel may take the launch."""
+    """heads: as head_tail_args plus w_first (16x16x32 fragments [16][K_pad/32]..., or the mx operand stream), b_first (256 f32),
+    w_out_perm and mfma16.  layout3x3 (default: every head carries w_out_perm): the slots are pack_conv_bf16's canonical order
+    for [feat 64 (, pc_hm 8)] sources - what the 2-D patch kernel implies.  cf_head_fused runs layout3x3 = 1 with mfma16 = 1
+    only and refuses every other form."""
     f = _lib.HeadFusedArgs()
     t = head_tail_args(srcs[0], 256, B, H, W, [dict(hd, c_base=0) for hd in heads])
     C.memmove(C.byref(f.tail), C.byref(t), C.sizeof(t))
@@ -234,8 +211,7 @@ def head_fused_args(srcs, src_strides, slots, k_pad, B, H, W, heads, layout3x3=N
         if hd.get("w_out_perm") is not None:
             f.w_out_perm[i] = hd["w_out_perm"].data_ptr()
     f.layout3x3 = int(all(hd.get("w_out_perm") is not None for hd in heads)) if layout3x3 is None else int(layout3x3)
-    f.mfma16 = int(all(bool(hd.get("mfma16")) for hd in heads))     # fragments packed for the 16x16x32 shape (the C
-    # side refuses them on a launch that does not take the 3x3 patch kernel: nothing else can read them)
+    f.mfma16 = int(all(bool(hd.get("mfma16")) for hd in heads))     # fragments packed for the 16x16x32 shape
     f.mx = int(all(hd.get("first_scale") is not None for hd in heads))   # packing.pack_head_first_mx streams: srcs[0] = mx rows
     if f.mx:
         for i, hd in enumerate(heads):
@@ -258,10 +234,6 @@ def pack_feat_mx(feat, out=None, scale=None):
 
 def run_head_fused(f):
     _lib.check(_lib.load().cf_head_fused(C.byref(f), _lib.stream_ptr()), "cf_head_fused")
-
-
-def run_head_tail(a):
-    _lib.check(_lib.load().cf_head_tail(C.byref(a), _lib.stream_ptr()), "cf_head_tail")
 
 
 def dcn_args(pd: PackedDcn, x, offmask, om_stride, B, H, W, out, out_stride, act=ACT_RELU,

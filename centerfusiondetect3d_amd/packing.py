@@ -99,10 +99,11 @@ def pack_conv(weight, bias, sources: Sequence[Source], stride=1, pad=None, dilat
                       tuple(s.channels for s in sources))
 
 
-def pack_conv_bf16(weight, bias, sources: Sequence[Source], stride=1, pad=None, dilation=1,
-                   fragments=False) -> PackedConv:
-    """Packing for cf_conv2d_bf16x3: slots of 8 channels, weights [N_pad][2][K_pad] bf16 with
-    w = hi + lo (hi = rne(w), lo = rne(w - hi)).  Source.stride = channels per plane."""
+def pack_conv_bf16(weight, bias, sources: Sequence[Source], stride=1, pad=None, dilation=1, fragments=16) -> PackedConv:
+    """Packing of a head's first layer for cf_head_fused: slots of 8 channels in the canonical order (source, tap, channel
+    group), weights split as w = hi + lo (hi = rne(w), lo = rne(w - hi)) into bf16 planes and laid out as 16x16x32 MFMA
+    fragments (pack_fragments16; fragments = 16 is the only form).  Source.stride = channels per plane."""
+    assert fragments == 16, "cf_head_fused reads 16x16x32 fragments only"
     co, ci, kh, kw = weight.shape
     assert ci == sum(s.channels for s in sources), (ci, [s.channels for s in sources])
     pad = (kh - 1) // 2 * dilation if pad is None else pad
@@ -124,7 +125,7 @@ def pack_conv_bf16(weight, bias, sources: Sequence[Source], stride=1, pad=None, 
             cols.append((-1, 0, 0, 0))
             n_slots += 1
         c_lo += s.channels
-    while len(slots) % 8:                  # whole 64-deep steps for the BK = 64 main loop
+    while len(slots) % 8:                  # K_pad a multiple of 64 (cf_head_fused checks it)
         slots.append([len(sources) - 1, 0, 0, -1])
         cols.append((-1, 0, 0, 0))
     k_pad = len(slots) * 8
@@ -135,15 +136,7 @@ def pack_conv_bf16(weight, bias, sources: Sequence[Source], stride=1, pad=None, 
             w[:co, 8 * j:8 * j + real] = wf[:, c0:c0 + real, r, q]
     b = torch.zeros(n_pad)
     b[:co] = bias
-    if fragments == 16:    # cf_head_fused with mfma16: 16x16x32 fragments
-        wt = pack_fragments16(w)
-    elif fragments:        # cf_head_fused: A-operand fragment order instead of [N][2][K]
-        wt = pack_fragments(w)
-    else:
-        hi = w.to(torch.bfloat16)
-        lo = (w - hi.float()).to(torch.bfloat16)
-        wt = torch.stack([hi, lo], dim=1).contiguous()
-    return PackedConv(wt, b, torch.tensor(slots, dtype=torch.int32), co, n_pad, k_pad, kh, stride, pad,
+    return PackedConv(pack_fragments16(w), b, torch.tensor(slots, dtype=torch.int32), co, n_pad, k_pad, kh, stride, pad,
                       tuple(s.channels for s in sources))
 
 
@@ -225,29 +218,6 @@ def pack_conv_f16(weight, bias, sources: Sequence[Source], stride=1, pad=None, d
         pc.real_cin = (sources[0].channels, proj[2].channels)
         pc.proj_k = proj[2].channels
     return pc
-
-
-def pack_fragments(weight2d, n_pad=None, acc_order=False):
-    """(N, K) fp32 -> MFMA A-operand fragment order for cf_head_tail:
-    uint8 view of [N_pad/32][K/16][2 (hi, lo)][64 lanes][8 bf16]; lane (i = l & 31, h = l >> 5)
-    holds W[32 rt + i][16 ks + 8 h + j], j = 0..7.
-    acc_order: position 8h + j of every 16-group holds channel 4h + (j & 3) + 8 (j >> 2) instead - the
-    order in which a 32x32 accumulator's register group presents its rows (cf_head_fused w_out_perm)."""
-    n, k = weight2d.shape
-    assert k % 16 == 0
-    n_pad = n_pad or ((n + 31) // 32) * 32
-    w = torch.zeros(n_pad, k)
-    w[:n] = weight2d.float()
-    if acc_order:
-        perm = torch.tensor([16 * g + 4 * hh + (j & 3) + 8 * (j >> 2)
-                             for g in range(k // 16) for hh in range(2) for j in range(8)])
-        w = w[:, perm]
-    hi = w.to(torch.bfloat16)
-    lo = (w - hi.float()).to(torch.bfloat16)
-    planes = torch.stack([hi, lo], 0)                                   # (2, N, K)
-    f = planes.view(2, n_pad // 32, 32, k // 16, 2, 8)                  # p, rt, i, ks, h, j
-    f = f.permute(1, 3, 0, 4, 2, 5).contiguous()                        # rt, ks, p, h, i, j
-    return f.view(n_pad // 32, k // 16, 2, 64, 8)
 
 
 def pack_fragments16(weight2d, n_pad=None, acc_order=False):

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define CF_ABI_VERSION 6 /* 2: cf_dcn_args.mask_activated, cf_nchw_to_nhwc, cf_spin_us; 3: cf_conv3x3_root_f16x3, stride 2 in cf_conv3x3_f16x3; 4: cf_head_fused_args.mx / first_scale, cf_pack_feat_mx, cf_dcn_args.out_mx; 5: cf_conv3x3_proj_f16x3, cf_stem_args.out_pool, cf_pack_conv_f16x3, cf_pack_dcn_f16; 6: in_scale (per-layer activation pre-scale of the f16x3 kernels) in cf_conv_args / cf_dcn_args / cf_stem_args, cf_dcn_args.mx_scale, cf_pack_feat_mx_scaled, cf_absmax_f32, cf_checksum64, cf_topk_peaks_if_changed, cf_topk_frustum */
+#define CF_ABI_VERSION 7 /* 2: cf_dcn_args.mask_activated, cf_nchw_to_nhwc, cf_spin_us; 3: cf_conv3x3_root_f16x3, stride 2 in cf_conv3x3_f16x3; 4: cf_head_fused_args.mx / first_scale, cf_pack_feat_mx, cf_dcn_args.out_mx; 5: cf_conv3x3_proj_f16x3, cf_stem_args.out_pool, cf_pack_conv_f16x3, cf_pack_dcn_f16; 6: in_scale (per-layer activation pre-scale of the f16x3 kernels) in cf_conv_args / cf_dcn_args / cf_stem_args, cf_dcn_args.mx_scale, cf_pack_feat_mx_scaled, cf_absmax_f32, cf_checksum64, cf_topk_peaks_if_changed, cf_topk_frustum; 7: the exports cf_conv2d_bf16x3 and cf_head_tail (CF_EINVAL stubs since ABI 6) removed, with CF_LAYOUT_NHWC_SPLIT_BF16 (an out_layout only the former took); nothing else changed */
 
 #define CF_OK 0
 #define CF_EINVAL (-22)
@@ -39,7 +39,6 @@ extern "C" {
 
 #define CF_LAYOUT_NHWC 0
 #define CF_LAYOUT_NCHW 1
-#define CF_LAYOUT_NHWC_SPLIT_BF16 2 /* per pixel [C hi][C lo] bf16, x = hi + lo (cf_conv2d_bf16x3) */
 
 /* One 16-byte K-slot of the implicit GEMM: 4 consecutive channels of one source at one tap. */
 typedef struct cf_slot {
@@ -107,18 +106,6 @@ typedef struct cf_stem_args {
                                      and of level0's output; scale_* = 2^-s / in_scale[i] of the layer that reads it */
 } cf_stem_args;
 int cf_stem_fused(const cf_stem_args* a, void* stream);
-
-/* cf_conv2d_bf16x3: the same implicit GEMM on the bf16 MFMA pipe with split operands
- * (x = hi + lo, both bf16; a*b ~= a_lo*b_hi + a_hi*b_lo + a_hi*b_hi, fp32 accumulate; <= ~2^-17
- * relative error per product at 5.3x the fp32-MFMA rate).  Used for the head convolutions
- * (model/networks/detectHeads.py:59-98, 165-191), which are not followed by the error-amplifying
- * DCN neck.  Same argument block as cf_conv2d_fused, read as follows: src[] are split-bf16 NHWC
- * tensors (src_c = channels per plane, multiple of 8); one slot = 8 channels; weight is
- * [N_pad][2][K_pad] bf16 (hi plane, lo plane); out is either CF_LAYOUT_NHWC_SPLIT_BF16
- * (out_stride = channels per plane) or CF_LAYOUT_NCHW fp32; residual / precise are ignored. */
-int cf_conv2d_bf16x3(const cf_conv_args* a, void* stream);
-/* (ABI 6) LEGACY: the unfused heads of rounds 1-2.  Compiled only with -DCF_LEGACY_HEADS; the default library keeps the export and
- * answers it with CF_EINVAL ("legacy kernel path") - every bf16x3 layer of the path runs inside cf_head_fused. */
 
 /* cf_conv2d_f16x3: cf_conv2d_fused semantics (fp32 NHWC sources / residual / output, bias, ReLU) with
  * the products evaluated on the f16 MFMA pipe from split operands (x = hi + lo fp16 after a
@@ -208,22 +195,23 @@ int cf_pack_dcn_f16_info(int32_t cout, int32_t cin, cf_pack_info* info);
 int cf_pack_dcn_f16(const float* weight, const float* bias, const cf_pack_bn* bn, int32_t cout, int32_t cin,
                     void* weight_out, float* bias_out, cf_pack_info* info);
 
-/* cf_split_bf16: fp32 NHWC [M][in_stride] (C used) -> split-bf16 [M][2][Cs], channels C..Cs-1 zero. */
+/* cf_split_bf16: fp32 NHWC [M][in_stride] (C used) -> split-bf16 [M][2][Cs], channels C..Cs-1 zero.  "split-bf16": every
+ * value is carried as two bf16 numbers x = hi + lo (hi = rne(x), lo = rne(x - hi), 16 significant bits together; per pixel
+ * [Cs hi][Cs lo], the same bytes as fp32) - the operand format of cf_head_fused, whose products are evaluated as
+ * a*b ~= a_lo*b_hi + a_hi*b_lo + a_hi*b_hi with fp32 accumulation (<= ~2^-17 relative error per product). */
 int cf_split_bf16(const float* x, void* out, long M, int C, int in_stride, int Cs, void* stream);
 
-/* cf_head_tail: fused tail of up to CF_MAX_HEADS sibling heads:  x -> [ReLU(W x + b)] x n_hidden -> W_out x
- * + b_out (+ head activation), hidden width 256, on the bf16 MFMA pipe with split operands.  The
- * hidden maps stay in LDS (64-pixel tiles); only the (B, n_out, H, W) fp32 NCHW maps are written.
- * replaces the 1x1 layers of model/networks/detectHeads.py:64-71, 80-90 (one launch instead of
- * 3 per secondary head / 1 per primary head, and no hidden-map round trips through HBM).
- * x: split-bf16 NHWC (B,H,W,2,x_stride); head i reads channels [c_base[i], c_base[i]+256).
- * w_hidden / w_out: weights in MFMA fragment order (centerfusiondetect3d_amd/packing.py:
- * pack_fragments): [row tile of 32][k step of 16][hi,lo][lane 64][8 bf16]; w_out is one row tile
- * (n_out <= 32, zero padded); b_out has 32 floats. */
+/* cf_head_tail_args: the `tail` member of cf_head_fused_args - the layers behind a head group's first 3x3 convolution, for up
+ * to CF_MAX_HEADS sibling heads:  x -> [ReLU(W x + b)] x n_hidden -> W_out x + b_out (+ head activation), hidden width 256
+ * (the 1x1 layers of model/networks/detectHeads.py:64-71, 80-90).  There is no stand-alone launch for it: x / x_stride /
+ * c_base are not read (the hidden tile is produced in LDS by the fused launch and never written to HBM).
+ * w_hidden / w_out: weights in the fragment order of v_mfma_f32_16x16x32_bf16 (centerfusiondetect3d_amd/packing.py:
+ * pack_fragments16): [row tile of 16][k step of 32][hi,lo][lane 64][8 bf16]; w_hidden[][] is [16 tiles][8 k steps], w_out
+ * one row tile (n_out <= 16, zero padded); b_out has 32 floats. */
 #define CF_MAX_HEADS 12
 typedef struct cf_head_tail_args {
-  const void* x;
-  int32_t x_stride;
+  const void* x;                           /* not read */
+  int32_t x_stride;                        /* not read */
   int32_t B, H, W;
   int32_t n_heads;
   int32_t n_hidden;                        /* 0..2 hidden 256->256 layers per head */
@@ -231,44 +219,40 @@ typedef struct cf_head_tail_args {
   const float* b_hidden[CF_MAX_HEADS][2];
   const void* w_out[CF_MAX_HEADS];
   const float* b_out[CF_MAX_HEADS];
-  float* out[CF_MAX_HEADS];
+  float* out[CF_MAX_HEADS];                /* fp32 NCHW (B, n_out, H, W) */
   float* out2[CF_MAX_HEADS];               /* second output of CF_ACT_RAW_AND_SIGDEPTH heads, else NULL */
-  int32_t c_base[CF_MAX_HEADS];
+  int32_t c_base[CF_MAX_HEADS];            /* not read */
   int32_t n_out[CF_MAX_HEADS];
   int32_t act[CF_MAX_HEADS];
 } cf_head_tail_args;
-int cf_head_tail(const cf_head_tail_args* a, void* stream);
-/* (ABI 6) LEGACY as a stand-alone launch (CF_LEGACY_HEADS builds only; CF_EINVAL otherwise): the argument block lives on as
- * cf_head_fused_args.tail, whose layers run inside the fused launch. */
 
-/* cf_head_fused: a whole head group in one launch: 3x3 conv (sources -> 256) + ReLU, then the tail
- * of cf_head_tail (tail.x / tail.x_stride / tail.c_base are ignored: the hidden tile is produced in
- * LDS and never written to HBM).  replaces model/networks/detectHeads.py:59-98 end to end.
- * src[]: split-bf16 NHWC sources (feat [, pc_hm]); slots: 8-channel slots as for cf_conv2d_bf16x3,
- * K_pad a multiple of 64; w_first[i]: fragment-packed [256/32][K_pad/16] rows of head i in slot
- * order; b_first[i]: 256 floats. */
+/* cf_head_fused: a whole head group in one launch: 3x3 conv (sources -> 256) + ReLU, then the layers of `tail`, on the bf16
+ * MFMA pipe with split operands.  Only the (B, n_out, H, W) fp32 NCHW maps are written.  replaces
+ * model/networks/detectHeads.py:59-98 end to end (one launch instead of 2 per primary / 4 per secondary head, and no
+ * hidden-map round trips through HBM).
+ * src[]: split-bf16 NHWC sources (feat, 64 channels [, pc_hm, 8 channels]); w_first[i]: 16x16x32 fragments
+ * [256/16][K_pad/32] of head i in the canonical 3x3 slot order (packing.pack_conv_bf16); b_first[i]: 256 floats.
+ * ONE form runs: layout3x3 = 1 with mfma16 = 1 (mx = 0 or 1).  The fields can still spell the forms of earlier kernels
+ * (layout3x3 = 0: an arbitrary slot table; mfma16 = 0: 32x32x16 fragments): those calls return CF_EINVAL. */
 typedef struct cf_head_fused_args {
   cf_head_tail_args tail;
   const void* src[2];
   int32_t src_c[2];
   int32_t n_src;
-  const cf_slot* slots;
-  int32_t K_pad;
+  const cf_slot* slots;                    /* mx = 0: validated as before (non-NULL; 8-channel slots), not read by the kernel */
+  int32_t K_pad;                           /* mx = 0: validated as before - a multiple of 64, <= 2048, >= 576 (672 with pc_hm) */
   const void* w_first[CF_MAX_HEADS];
   const float* b_first[CF_MAX_HEADS];
-  int32_t layout3x3;                       /* 1: the slot order is the canonical one - src[0] (64 channels): 9 taps
-                                              x 8 slots, then src[1] (8 channels): 9 taps x 1 slot - so the launch
-                                              may run on the 2-D patch kernel (no slot table reads)                 */
-  const void* w_out_perm[CF_MAX_HEADS];    /* layout3x3 && n_hidden == 0: w_out with the k order of an accumulator
-                                              register group (position 8h+j of a 16-group = channel 4h+(j&3)+8(j>>2)) */
-  int32_t mfma16;                          /* layout3x3 only.  != 0: w_first[] and w_out_perm[] are packed for
+  int32_t layout3x3;                       /* must be 1: the slot order is the canonical one - src[0] (64 channels): 9 taps
+                                              x 8 slots, then src[1] (8 channels): 9 taps x 1 slot - which the 2-D patch
+                                              kernel implies (no slot table reads)                                       */
+  const void* w_out_perm[CF_MAX_HEADS];    /* n_hidden == 0: w_out as ONE 16-row tile whose k position (step ks, group g, j) holds
+                                              hidden channel 64 (ks >> 1) + 16 (2 (ks & 1) + (j >> 2)) + 4 g + (j & 3) - the order of
+                                              an accumulator register group (packing.pack_fragments16(acc_order=True))    */
+  int32_t mfma16;                          /* must be 1: w_first[], w_out_perm[], tail.w_hidden[][] and tail.w_out[] are packed for
                                               v_mfma_f32_16x16x32_bf16 - [16-row tile][k step of 32][hi,lo][lane 64][8 bf16],
-                                              lane l = row l & 15, k 8 (l >> 4) + j (packing.pack_fragments16); w_out_perm is
-                                              ONE 16-row tile whose k position (step ks, group g, j) holds hidden channel
-                                              64 (ks >> 1) + 16 (2 (ks & 1) + (j >> 2)) + 4 g + (j & 3); n_out <= 16; tail.w_hidden[][] ([16 tiles][8 k steps])
-                                              and tail.w_out[] (one 16-row tile, natural k order) are 16x16x32 fragments too.  The launch
-                                              then runs on the 16x16x32 patch kernel (1.14x the 32x32x16 rate under load) */
-  int32_t mx;                              /* layout3x3 && mfma16 only.  != 0: the FIRST layer runs as "fp16 main term + block-scaled FP6
+                                              lane l = row l & 15, k 8 (l >> 4) + j (packing.pack_fragments16); n_out <= 16 */
+  int32_t mx;                              /* != 0: the FIRST layer runs as "fp16 main term + block-scaled FP6
                                               cross terms" (v_mfma_f32_16x16x32_f16 + v_mfma_scale_f32_16x16x128_f8f6f4, 1.5 passes per
                                               product instead of 3): src[0] is the 272-byte-per-pixel image cf_pack_feat_mx writes
                                               (src_c[0] = 64), w_first[i] the operand stream of packing.pack_head_first_mx (slots / K_pad
@@ -277,9 +261,6 @@ typedef struct cf_head_fused_args {
   float first_scale[CF_MAX_HEADS];         /* mx: 2^-(s+4) of head i's first layer (applied where b_first is added) */
 } cf_head_fused_args;
 int cf_head_fused(const cf_head_fused_args* a, void* stream);
-/* (ABI 6) the default library runs the forms the host dispatches - layout3x3 = 1 with mfma16 = 1 (16x16x32 fragments, n_out <= 16),
- * mx = 0 or 1; the 32x32x16 patch kernel (mfma16 = 0) and the slot-table kernel (layout3x3 = 0) are CF_LEGACY_HEADS builds only
- * (CF_EINVAL otherwise). */
 
 /* cf_pack_feat_mx: fp32 NHWC feature map [M][in_stride] (64 channels used) -> [M][272] bytes for cf_head_fused with mx = 1:
  * per pixel four 64-byte segments g = 0..3 - [8 fp16: hi channels 8g..8g+7][8 fp16: hi channels 32+8g..32+8g+7][FP6 block g:

@@ -424,33 +424,39 @@ def test_split_bf16_roundtrip(dev):
 
 
 def test_legacy_head_kernels_are_not_in_the_default_build(dev):
-    """The kernels of rounds 1-3 that nothing dispatches any more - cf_conv2d_bf16x3 (unfused heads), cf_head_tail, cf_head_fused
-    on 32x32x16 fragments or on the slot table - are compiled only with -DCF_LEGACY_HEADS: the default library still exports the
-    entry points (include/cf_hip.h) and answers them with an error that says so, never with a wrong result."""
+    """The kernels of rounds 1-3 are gone: cf_conv2d_bf16x3 (unfused heads) and cf_head_tail are neither exported by the
+    library nor bound (ABI 7), and cf_head_fused refuses the two forms only those generations could run - 32x32x16 fragments
+    (mfma16 = 0) and the slot table (layout3x3 = 0) - before it reads a weight, never with a wrong result."""
     from centerfusiondetect3d_amd import ops, packing, _lib
+    lib = _lib.load()
+    for name in ("cf_conv2d_bf16x3", "cf_head_tail"):
+        assert name not in _lib.SYMBOLS
+        assert not hasattr(lib, name), name                          # (ctypes resolves by dlsym: no such export)
+    for name in ("run_conv_bf16", "conv2d_bf16x3", "run_head_tail"):
+        assert not hasattr(ops, name), name
     B, H, W = 1, 8, 16
     x = rnd(B, 64, H, W, seed=1)
     w, b = rnd(256, 64, 3, 3, seed=2, scale=1 / 24), rnd(256, seed=3)
-    pc = packing.pack_conv_bf16(w, b, [packing.Source(64, 64)]).to(dev)
-    with pytest.raises(_lib.CfHipError, match="legacy kernel path"):
-        ops.conv2d_bf16x3(pc, [_split(x, dev)], B, H, W, act=1)
-    hid = _split(F.relu(rnd(B, 256, H, W, seed=4)), dev)
     wo = rnd(8, 256, seed=5, scale=1 / 16)
-    head = dict(c_base=0, w_hidden=[], b_hidden=[], w_out=packing.pack_fragments(wo).to(dev), b_out=torch.zeros(32, device=dev),
-                n_out=8, act=0, out=torch.empty(B, 8, H, W, device=dev), out2=None)
-    with pytest.raises(_lib.CfHipError, match="legacy kernel path"):
-        ops.run_head_tail(ops.head_tail_args(hid, 256, B, H, W, [head]))
-    pc32 = packing.pack_conv_bf16(w, b, [packing.Source(64, 64)], fragments=True).to(dev)           # 32x32x16 fragments
-    h32 = dict(head, w_first=pc32.weight, b_first=pc32.bias[:256].contiguous(), w_out_perm=packing.pack_fragments(wo, acc_order=True).to(dev),
-               mfma16=False)
-    f = ops.head_fused_args([_split(x, dev)], [64], pc32.slots, pc32.k_pad, B, H, W, [h32])
-    assert f.layout3x3 == 1 and f.mfma16 == 0
-    with pytest.raises(_lib.CfHipError, match="legacy kernel path"):
+    pc = packing.pack_conv_bf16(w, b, [packing.Source(64, 64)]).to(dev)
+    out = torch.full((B, 8, H, W), float("nan"), device=dev)
+    head = dict(w_hidden=[], b_hidden=[], w_out=packing.pack_fragments16(wo).to(dev), b_out=torch.zeros(32, device=dev),
+                n_out=8, act=0, out=out, out2=None, w_first=pc.weight, b_first=pc.bias[:256].contiguous(),
+                w_out_perm=packing.pack_fragments16(wo, acc_order=True).to(dev), mfma16=True)
+    src = _split(x, dev)
+    f = ops.head_fused_args([src], [64], pc.slots, pc.k_pad, B, H, W, [head])
+    assert f.layout3x3 == 1 and f.mfma16 == 1
+    f.mfma16 = 0                                                     # the 16-form packs with the flag cleared
+    with pytest.raises(_lib.CfHipError, match=r"layout3x3 = 1 .* mfma16 = 1 .*only.*mfma16 = 0"):
         ops.run_head_fused(f)
-    f0 = ops.head_fused_args([_split(x, dev)], [64], pc32.slots, pc32.k_pad, B, H, W, [dict(h32, w_out_perm=None)])
-    assert f0.layout3x3 == 0
-    with pytest.raises(_lib.CfHipError, match="legacy kernel path"):
+    f0 = ops.head_fused_args([src], [64], pc.slots, pc.k_pad, B, H, W, [head])
+    f0.layout3x3, f0.mfma16 = 0, 0
+    with pytest.raises(_lib.CfHipError, match=r"layout3x3 = 1 .* mfma16 = 1 .*only.*layout3x3 = 0"):
         ops.run_head_fused(f0)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(out).all())                              # refused: nothing was launched
+    ops.run_head_fused(ops.head_fused_args([src], [64], pc.slots, pc.k_pad, B, H, W, [head]))   # the accepted form runs
+    assert bool(torch.isfinite(out).all())
 
 
 @pytest.mark.parametrize("n_hidden,radar,B,H,W,patch", [
@@ -462,9 +468,8 @@ def test_legacy_head_kernels_are_not_in_the_default_build(dev):
 ])
 def test_head_fused_whole_head(dev, n_hidden, radar, B, H, W, patch):
     """3x3 conv (feat [|| pc_hm]) + ReLU -> hidden chain -> output, one launch, vs fp32 torch: the 2-D LDS-patch kernel on
-    v_mfma_f32_16x16x32_bf16 fragments (patch == 16; the 32x32x16 and slot-table forms of rounds 1-3 are legacy builds only)."""
-    m16 = patch == 16
-    patch = bool(patch)
+    v_mfma_f32_16x16x32_bf16 fragments (patch == 16: the only form cf_head_fused runs; the parameter keeps the case ids)."""
+    assert patch == 16
     from centerfusiondetect3d_amd import ops, packing
     n_outs, acts = [10, 1, 3, 8], [2, 3, 0, 0]
     feat, pch = rnd(B, 64, H, W, seed=1), rnd(B, 3, H, W, seed=2)
@@ -476,43 +481,41 @@ def test_head_fused_whole_head(dev, n_hidden, radar, B, H, W, patch):
     for i, (no, act) in enumerate(zip(n_outs, acts)):
         w1, b1 = rnd(256, ci, 3, 3, seed=300 + i, scale=(ci * 9) ** -0.5), rnd(256, seed=310 + i, scale=0.1)
         x = F.relu(F.conv2d(xin, w1, b1, 1, 1))
-        pc = packing.pack_conv_bf16(w1, b1, sources, fragments=16 if m16 else True).to(dev)
+        pc = packing.pack_conv_bf16(w1, b1, sources).to(dev)
         slots, k_pad = pc.slots, pc.k_pad
         wh, bh = [], []
         for l in range(n_hidden):
             w, b = rnd(256, 256, 1, 1, seed=10 * i + l, scale=1 / 16), rnd(256, seed=50 + 10 * i + l, scale=0.1)
             x = F.relu(F.conv2d(x, w, b))
-            wh.append((packing.pack_fragments16 if m16 else packing.pack_fragments)(w.view(256, 256)).to(dev)); bh.append(b.to(dev))
+            wh.append(packing.pack_fragments16(w.view(256, 256)).to(dev)); bh.append(b.to(dev))
         w, b = rnd(no, 256, 1, 1, seed=100 + i, scale=1 / 16), rnd(no, seed=200 + i)
         raw = F.conv2d(x, w, b)
         b32 = torch.zeros(32); b32[:no] = b
         out = torch.full((B, no, H, W), float("nan"), device=dev)
         out2 = torch.full((B, no, H, W), float("nan"), device=dev) if act == 3 else None
         heads.append(dict(w_first=pc.weight, b_first=pc.bias[:256].contiguous(), w_hidden=wh, b_hidden=bh,
-                          w_out=(packing.pack_fragments16 if m16 else packing.pack_fragments)(w.view(no, 256)).to(dev), b_out=b32.to(dev),
-                          w_out_perm=((packing.pack_fragments16 if m16 else packing.pack_fragments)(
-                              w.view(no, 256), acc_order=True).to(dev) if patch else None),
-                          mfma16=m16, n_out=no, act=act, out=out, out2=out2))
+                          w_out=packing.pack_fragments16(w.view(no, 256)).to(dev), b_out=b32.to(dev),
+                          w_out_perm=packing.pack_fragments16(w.view(no, 256), acc_order=True).to(dev),
+                          mfma16=True, n_out=no, act=act, out=out, out2=out2))
         refs.append(raw)
     f = ops.head_fused_args(srcs, [s.shape[-1] for s in srcs], slots, k_pad, B, H, W, heads)
-    assert f.layout3x3 == int(patch) and f.mfma16 == int(m16)
-    if m16:
-        # the 128-pixel tile lies flat (8 x 16) or stands upright (16 x 8), whichever needs fewer tiles: force both,
-        # the results must not differ by a bit
-        firsts = None
-        for tile in ("0", "1"):
-            os.environ["CF_HEAD_TILE"] = tile
-            try:
-                for hd in heads:
-                    hd["out"].fill_(float("nan"))
-                ops.run_head_fused(f)
-            finally:
-                del os.environ["CF_HEAD_TILE"]
-            outs = [hd["out"].clone() for hd in heads] + [hd["out2"].clone() for hd in heads if hd["out2"] is not None]
-            if firsts is None:
-                firsts = outs
-            else:
-                assert all(torch.equal(a, b) for a, b in zip(firsts, outs))
+    assert f.layout3x3 == 1 and f.mfma16 == 1
+    # the 128-pixel tile lies flat (8 x 16) or stands upright (16 x 8), whichever needs fewer tiles: force both,
+    # the results must not differ by a bit
+    firsts = None
+    for tile in ("0", "1"):
+        os.environ["CF_HEAD_TILE"] = tile
+        try:
+            for hd in heads:
+                hd["out"].fill_(float("nan"))
+            ops.run_head_fused(f)
+        finally:
+            del os.environ["CF_HEAD_TILE"]
+        outs = [hd["out"].clone() for hd in heads] + [hd["out2"].clone() for hd in heads if hd["out2"] is not None]
+        if firsts is None:
+            firsts = outs
+        else:
+            assert all(torch.equal(a, b) for a, b in zip(firsts, outs))
     ops.run_head_fused(f)
     for hd, raw in zip(heads, refs):
         scale = float(raw.abs().max())
@@ -535,7 +538,7 @@ def test_head_fused_refuses_mfma16_fragments_it_cannot_read(dev):
     feat = rnd(B, 64, H, W, seed=1)
     srcs = [_split(feat, dev)]
     w1, b1 = rnd(256, 64, 3, 3, seed=2, scale=1 / 24), rnd(256, seed=3)
-    pc = packing.pack_conv_bf16(w1, b1, [packing.Source(64, 64)], fragments=16).to(dev)
+    pc = packing.pack_conv_bf16(w1, b1, [packing.Source(64, 64)]).to(dev)
 
     def head(n_out, n_hidden, perm=True):
         w = rnd(n_out, 256, 1, 1, seed=4, scale=1 / 16)

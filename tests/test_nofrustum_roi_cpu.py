@@ -80,7 +80,7 @@ def test_detector_hands_the_configured_method_on_and_no_key_means_pillars(method
 def test_new_entry_points_validate_their_arguments_without_gpu():
     from centerfusiondetect3d_amd import _lib
     lib = _lib.load()
-    assert lib.cf_abi_version() == 6
+    assert lib.cf_abi_version() == 7
     buf = (ctypes.c_float * 64)()
     p = ctypes.addressof(buf)
     assert lib.cf_pc_hm_direct(None, 1, 4, 4, 60.0, None, None, None) == -22

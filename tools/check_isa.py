@@ -14,7 +14,7 @@ import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "centerfusiondetect3d_amd", "csrc")
-SOURCES = {"cf_conv3x3_f16.hip": ("conv3x3_f16x3_kernel",), "cf_heads.hip": ("head_patch_kernel", "head_patch16_kernel"),
+SOURCES = {"cf_conv3x3_f16.hip": ("conv3x3_f16x3_kernel",), "cf_heads.hip": ("head_patch16_kernel",),
            "cf_gemm_f16.hip": ("dcn_f16x3_kernel", "conv_f16x3_kernel"), "cf_post.hip": ("pc_hm_direct_kernel",)}
 
 
@@ -52,7 +52,7 @@ def violations(lines):
 EPILOGUE_KERNELS = ("conv_f16x3_kernel", "dcn_f16x3_kernel", "conv3x3_f16x3_kernel")
 # kernels whose MFMA loop must be free of scratch traffic (every instantiation the default path launches)
 # kernels of the default path: NO instantiation may use scratch at all (ScratchSize 0 in the compiler's resource summary)
-NO_SCRATCH = ("head_patch16_kernel", "head_patch_kernel", "dcn_f16x3_kernel", "conv3x3_f16x3_kernel", "conv_f16x3_kernel",
+NO_SCRATCH = ("head_patch16_kernel", "dcn_f16x3_kernel", "conv3x3_f16x3_kernel", "conv_f16x3_kernel",
               "pc_hm_direct_kernel")
 
 
