@@ -27,7 +27,7 @@ def _peaks_and_maps(outputs, K):
         raise NotImplementedError("uncertainty head (TRAIN.UNCERTAINTY_LOSS) is outside the hot path")
     heat = out["heatmap"]
     _, _, H, W = heat.shape
-    # The forward may have computed exactly these peaks already, beside its own launches (model._Plan.run: the heat map tensor
+    # The forward may have computed exactly these peaks already, beside its own launches (plan._Plan.run: the heat map tensor
     # carries them with a checksum of the bits they were computed from).  They are used only for the very tensor object, and
     # only while its contents still have that checksum: the map is summed again here and the guard launch that follows
     # compares the two sets of partial sums ON THE DEVICE - equal: it returns at once and the carried peaks stand; different (an

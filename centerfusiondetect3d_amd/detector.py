@@ -181,11 +181,11 @@ class Detector(object):
             device never waits for the host.
         The reference gets the same overlap from its DataLoader workers + pinned memory (trainer.py, dataset/); frames
         should sit in pinned host memory for the copy to be asynchronous.  An extension: not in the reference's API."""
-        from .model import _side_streams
+        from .streams import _side_streams
         it = iter(batches)
 
         def feed_stream(main):
-            # one stream past the model's own side streams, probed (model._pick_streams) to run beside them AND beside
+            # one stream past the model's own side streams, probed (streams._pick_streams) to run beside them AND beside
             # `main`, where the heads and the decode are
             n = max(int(getattr(self.model, "streams", 2)), 2) + 1
             return _side_streams(self.device, main.cuda_stream, n)[n - 1]

@@ -14,19 +14,19 @@ argument block of every kernel launch, and from then on a forward pass is a flat
 asynchronous launches on the current stream (no allocation except the returned head maps, no host
 sync, hipGraph-capturable).  There is no CPU fallback: without libcfhip.so / a GPU it raises.
 """
-import ctypes as C
 import math
 import threading
-from typing import Dict, List
+from typing import List
 
 import torch
 from torch import nn
 
 from . import _lib, ops, packing
-from ._lib import (ACT_NONE, ACT_RELU, ACT_SIGMOID_CLAMP, ACT_RAW_AND_SIGDEPTH, LAYOUT_NHWC, LAYOUT_NCHW)
 from .packing import Source
+from .plan import SECONDARY_HEADS, _Plan, feat_operand
+from .streams import (_CAPTURE_LOCK, _PROBE_LOG, _PROBE_US, _SIDE_STREAMS,     # (tests and tools reach these through this module)
+                      _concurrent, _pick_streams, _side_streams)
 
-SECONDARY_HEADS = ["velocity", "nuscenes_att", "depth2", "rotation2"]   # detectHeads.py:146-153
 CHANNELS = [16, 32, 64, 128, 256, 512]                                    # dla.py:303-307
 
 
@@ -149,703 +149,6 @@ def _param_spec(config) -> List[tuple]:
     return spec
 
 
-# ----------------------------------------------------------------------------- execution plan
-_SIDE_STREAMS = {}    # (device, caller stream id) -> probed side streams, LRU of _SIDE_KEYS keys per PROCESS
-_SIDE_KEYS = 16
-_SIDE_LOCK = threading.Lock()
-_CAPTURE_LOCK = threading.RLock()   # held while a stream captures AND while a captured graph is destroyed (see _forward_graph)
-_PROBE_US = 300       # length of one probe spin; two of them take ~1x this when concurrent, ~2x when serialised
-_PROBE_LOG = []       # [(device, sid, n, chosen indices, [(i, j, ms)])]: what the probes measured (tests / DESIGN)
-
-
-def _concurrent(lib, a, b, us=_PROBE_US):
-    """True if a `cf_spin_us` on stream `a` and one on stream `b`, issued back to back, overlap in time.  HIP maps
-    streams onto a few hardware queues; two streams that share one run their kernels strictly one after the other
-    (model.streams = 2 then measures 10.5 instead of 8.5 ms per bs=16 step).  -> (bool, ms from first start to last end)"""
-    e0, e1a, e1b = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-    gate = torch.cuda.Event()
-    gate.record(a)
-    b.wait_event(gate)                       # neither spin starts before both streams have drained to here
-    e0.record(a)
-    _lib.check(lib.cf_spin_us(us, a.cuda_stream), "cf_spin_us")
-    e1a.record(a)
-    _lib.check(lib.cf_spin_us(us, b.cuda_stream), "cf_spin_us")
-    e1b.record(b)
-    e1a.synchronize()
-    e1b.synchronize()
-    ms = max(e0.elapsed_time(e1a), e0.elapsed_time(e1b))
-    return ms < 1.6e-3 * us, ms
-
-
-def _pick_streams(device, cur, n, pool):
-    """Extend `pool` to n streams that run concurrently with each other and with the caller's stream `cur` (the
-    two-lane neck issues on `cur` and on pool[0]; the heads, the decode and `Detector.run_pipelined`'s consumer run on
-    `cur` beside whatever the last pool stream feeds).  Candidates are taken from torch's stream pool
-    one at a time and kept only if a pair of spin kernels says they overlap with everything chosen so far - whatever
-    else of the process (RCCL's communicator stream, other models, user streams) already sits on the hardware queues.
-    Falls back to plain creation order if no concurrent set turns up within 12 candidates (still correct, only slower)."""
-    lib = _lib.load()
-    tried, log = [], []
-    with _CAPTURE_LOCK:                       # the probe synchronises: never beside another thread's stream capture
-        torch.cuda.synchronize(device)
-        while len(pool) < n and len(tried) < 12:
-            c = torch.cuda.Stream(device)
-            tried.append(c)
-            ok = True
-            for x in [cur] + pool:
-                good, ms = _concurrent(lib, x, c)
-                log.append((len(tried) - 1, "caller" if x is cur else pool.index(x), round(ms, 3)))
-                if not good:
-                    ok = False
-                    break
-            if ok:
-                pool.append(c)
-    fallback = len(pool) < n
-    for c in tried:                           # not enough concurrent ones: take what was created, in order
-        if len(pool) >= n:
-            break
-        if c not in pool:
-            pool.append(c)
-    _PROBE_LOG.append((str(device), int(cur.cuda_stream), n, fallback, log))
-    del _PROBE_LOG[:-32]
-    return pool
-
-
-def _side_streams(device, sid, n):
-    """The n side streams that work issued on caller stream `sid` of `device` forks onto.  One set per process and caller
-    stream, not per model or plan, chosen ONCE by a probe (`_pick_streams`) instead of by creation order: HIP spreads
-    streams over a few hardware queues, whether two side streams share a queue decides whether their kernels overlap
-    at all (8.5 vs 10.5 ms per bs=16 step), and under torchrun RCCL has taken streams before the first model exists.
-    During a graph capture nothing may synchronise: fresh streams are forked as they come (the replay's placement is
-    the graph executor's, not these streams')."""
-    key = (str(device), int(sid))
-    with _SIDE_LOCK:                              # the common case: the set exists
-        pool = _SIDE_STREAMS.get(key)
-        if pool is not None and len(pool) >= n:
-            _SIDE_STREAMS[key] = _SIDE_STREAMS.pop(key)          # re-inserted last: dict order is the LRU order
-            return pool[:n]
-    # streams are missing: the probe synchronises the device, which must not happen beside another thread's stream
-    # capture - lock order is _CAPTURE_LOCK, then _SIDE_LOCK, everywhere (a capturing thread holds the first already)
-    with _CAPTURE_LOCK, _SIDE_LOCK:
-        pool = _SIDE_STREAMS.pop(key, [])
-        if len(pool) < n:
-            if torch.cuda.is_current_stream_capturing():
-                while len(pool) < n:
-                    pool.append(torch.cuda.Stream(device))
-            else:
-                pool = _pick_streams(device, torch.cuda.current_stream(device), n, pool)
-        _SIDE_STREAMS[key] = pool
-        while len(_SIDE_STREAMS) > _SIDE_KEYS:
-            _SIDE_STREAMS.pop(next(iter(_SIDE_STREAMS)))
-        return pool[:n]
-
-
-class _Plan:
-    """Buffers + pre-built launch list for one (B, H, W, device)."""
-
-    def __init__(self, model: "DLASeg", B, H, W, device, part="all", feat=None, feat_in=None):
-        """part: "all" (one plan per forward), or the two halves of the split forward (DLASeg.streams > 1):
-        "trunk" = backbone + neck of a sub-batch, its last DCN writing the feature map (and its split-bf16 copy)
-        into the caller's `feat` / `feat_in` slices; "heads" = everything behind the feature map for the WHOLE
-        batch, reading the full `feat` / `feat_in` buffers the trunks filled."""
-        self.B, self.H, self.W, self.device = B, H, W, device
-        self.part = part
-        self.lib = _lib.load()
-        self.steps = []          # (fn, args...) tuples executed in order (stream appended at run)
-        self.lanes = []          # per step: 0 = the caller's stream, 1 = the plan's side stream (see ida())
-        self.lane = 0
-        self.n_events = 0
-        # two-lane issue of the neck for small batches (a launch cannot fill the chip there); never with the timed /
-        # graph paths, which want one stream
-        # (a trunk sub-batch of the two-stream forward keeps round 5's limit of 4 frames: its side lane would be a third / fourth
-        #  stream beside the other trunk, and the event traffic of that costs more than the overlap gives)
-        self.use_lanes = bool(model.lanes) and part != "heads" and \
-            B * (H // 4) * (W // 4) <= (model.lanes_max_frames if part == "all" else min(4, model.lanes_max_frames)) * 112 * 200
-        self.keep = []           # keeps arg blocks / buffers alive
-        self.bytes = 0
-        self.step_index = {}     # conv name -> index in self.steps
-        self.step_flops = {}     # conv name -> algorithmic FLOPs of that launch (2*MACs)
-        self.timed = {}          # step index -> [(start_event, end_event)] filled while timing is on
-        self.inputs = {}         # layer name -> the resident NHWC tensors that layer's GEMM reads (DLASeg.activation_ranges)
-        self.hidden = set()      # layer names with operands that never reach HBM in this plan (fused intermediates)
-        pk = model._packed
-        cfg = model.config
-        heads, head_conv = dict(cfg.heads), {k: list(v) for k, v in cfg.head_conv.items()}
-        radar = model.isRadarEnabled and model.fusionStrategy == "middle"
-        frustum = radar and model.isFrustumEnabled     # False on a radar model: the radar map itself is pc_hm (base_model.py:69-79)
-        K = int(cfg.MODEL.K)
-
-        def buf(*shape, dtype=torch.float32):
-            t = torch.empty(shape, device=device, dtype=dtype)
-            self.bytes += t.numel() * t.element_size()
-            self.keep.append(t)
-            return t
-
-        def conv(name, srcs, h, w, act=ACT_RELU, residual=None, out=None, out_stride=None,
-                 out_offset=0, layout=LAYOUT_NHWC, out2=None, strides=None, precise=None):
-            # everything that feeds the DCN neck sums in two levels (cf_gemm.hip: PRECISE); the
-            # heads come after it, their rounding is not amplified
-            precise = (model.precise and not name.startswith("heads.")) if precise is None else precise
-            pc = pk[name]
-            ho = (h + 2 * pc.pad - pc.kh) // pc.stride + 1
-            wo = (w + 2 * pc.pad - pc.kh) // pc.stride + 1
-            if out is None:
-                out = buf(B, ho, wo, pc.n)
-            a = ops.conv_args(pc, srcs, strides or [s.shape[-1] for s in srcs], B, h, w, out,
-                              out_stride or pc.n, act, residual,
-                              residual.shape[-1] if residual is not None else 0, layout, out2,
-                              out_offset, precise, in_scale=model._scale(name) if pc.out_scale > 0 else None)
-            self.keep.append(a)
-            self.inputs[name] = list(srcs)
-            self.step_index[name] = len(self.steps)
-            self.step_flops[name] = 2.0 * B * ho * wo * pc.n * (pc.kh * pc.kh * sum(
-                int(c) for c in pc.real_cin))
-            fn = self.lib.cf_conv2d_fused
-            if pc.out_scale > 0:
-                fn = self.lib.cf_conv3x3_f16x3 if (pc.patch and model.conv_patch) else self.lib.cf_conv2d_f16x3
-            self.add_step((fn, C.byref(a)))
-            return out, a
-
-        pooled = {}
-
-        def pool(x):
-            # (a two-level Tree pools its input for its own Root AND its first sub-tree pools the same tensor again,
-            #  dla.py:96,107 at both nesting levels: one launch serves both)
-            if x.data_ptr() in pooled:
-                return pooled[x.data_ptr()]
-            _, h, w, c = x.shape
-            o = buf(B, h // 2, w // 2, c)
-            self.add_step((self.lib.cf_maxpool2x2, x.data_ptr(), o.data_ptr(), B, h, w, c))
-            pooled[x.data_ptr()] = o
-            return o
-
-        def block(p, x, residual, pooled=None):
-            _, h, w, _ = x.shape
-            t, _ = conv(p + ".conv1", [x], h, w)
-            _, ho, wo, _ = t.shape
-            if pooled is not None:
-                # conv2 + the Tree's project of the pooled input in one step (weights packed together: _prepare.tree1)
-                pc = pk[p + ".conv2"]
-                o = buf(B, ho, wo, pc.n)
-                a = ops.conv_args(pc, [t, pooled], [t.shape[-1], pooled.shape[-1]], B, ho, wo, o, pc.n, ACT_RELU, None, 0,
-                                  LAYOUT_NHWC, None, 0, False, in_scale=model._scale(p + ".conv2"))   # (one pre-scale for both parts)
-                self.inputs[p + ".conv2"], self.inputs[p[:-len(".tree1")] + ".project"] = [t], [pooled]
-                ch = (C.c_int32 * 2)(*[int(c) for c in pc.real_cin])
-                self.keep += [a, ch]
-                name = p + ".conv2+project"
-                self.step_index[name] = len(self.steps)
-                self.step_flops[name] = 2.0 * B * ho * wo * pc.n * (9 * pc.real_cin[0] + pc.real_cin[1])
-                if model.conv_patch:
-                    self.add_step((self.lib.cf_conv3x3_proj_f16x3, C.byref(a), ch))
-                else:
-                    self.add_step((self.lib.cf_conv2d_f16x3, C.byref(a)))
-                return o
-            o, _ = conv(p + ".conv2", [t], ho, wo, residual=residual if residual is not None else x)
-            return o
-
-        def tree(p, levels, x, stride, level_root, children=None):
-            children = [] if children is None else children
-            bottom = pool(x) if stride > 1 else x
-            proj_fused = levels == 1 and getattr(pk[p + ".tree1.conv2"], "proj_k", 0) > 0
-            if proj_fused:
-                residual = None
-            elif (p + ".project") in pk:
-                _, h, w, _ = bottom.shape
-                residual, _ = conv(p + ".project", [bottom], h, w, act=ACT_NONE)
-            else:
-                residual = bottom
-            if level_root:
-                children.append(bottom)
-            if levels == 1:
-                x1 = block(p + ".tree1", x, residual, pooled=bottom if proj_fused else None)
-                pc2, pcr = pk[p + ".tree2.conv2"], pk[p + ".root"]
-                if (model.root_fuse and model.conv_patch and pc2.out_scale > 0 and pcr.out_scale > 0
-                        and getattr(pc2, "patch", False) and pc2.stride == 1
-                        and (not children or model.root_fuse_children)):
-                    # tree2.conv2 and the Root as ONE step (cf_conv3x3_root_f16x3): x2 is never written where a workgroup
-                    # holds every channel of its pixels (64 / 128 / 256 channels: levels 2-4; children are read from HBM
-                    # inside the launch); the library runs the two launches for every other shape, bit-identical either way
-                    _, h, w, _ = x1.shape
-                    t, _ = conv(p + ".tree2.conv1", [x1], h, w)
-                    x2, o = buf(B, h, w, pc2.n), buf(B, h, w, pcr.n)
-                    a2 = ops.conv_args(pc2, [t], [t.shape[-1]], B, h, w, x2, pc2.n, ACT_RELU, x1, x1.shape[-1],
-                                       LAYOUT_NHWC, None, 0, False, in_scale=model._scale(p + ".tree2.conv2"))
-                    rsrcs = [x2, x1, *children]
-                    ar = ops.conv_args(pcr, rsrcs, [s_.shape[-1] for s_ in rsrcs], B, h, w, o, pcr.n, ACT_RELU, None, 0,
-                                       LAYOUT_NHWC, None, 0, False, in_scale=model._scale(p + ".root"))
-                    self.inputs[p + ".tree2.conv2"], self.inputs[p + ".root"] = [t], [x1, *children]
-                    self.hidden.add(p + ".root")             # (x2 stays on the chip)
-                    rch = (C.c_int32 * len(rsrcs))(*[int(c) for c in pcr.real_cin])
-                    self.keep += [a2, ar, rch]
-                    name = p + ".tree2.conv2+root"
-                    self.step_index[name] = len(self.steps)
-                    self.step_flops[name] = 2.0 * B * h * w * (pc2.n * 9 * sum(int(c) for c in pc2.real_cin)
-                                                               + pcr.n * sum(int(c) for c in pcr.real_cin))
-                    self.add_step((self.lib.cf_conv3x3_root_f16x3, C.byref(a2), C.byref(ar), rch))
-                    return o
-                x2 = block(p + ".tree2", x1, None)
-                _, h, w, _ = x2.shape
-                o, _ = conv(p + ".root", [x2, x1, *children], h, w)
-                return o
-            x1 = tree(p + ".tree1", levels - 1, x, stride, False)
-            children.append(x1)
-            return tree(p + ".tree2", levels - 1, x1, 1, False, children)
-
-        def dcn_node(p, x, out=None, feat_producer=False):
-            _, h, w, c = x.shape
-            om = buf(B, h, w, 32)
-            conv(p + ".conv_offset_mask", [x], h, w, act=ACT_NONE, out=om, out_stride=32)
-            pd = pk[p]
-            o = buf(B, h, w, pd.n) if out is None else out
-            ws = None
-            if pd.out_scale > 0:
-                nbytes = self.lib.cf_dcn_v2_workspace_bytes(B, h, w, pd.c, pd.n_pad)
-                ws = buf(nbytes, dtype=torch.uint8) if nbytes else None
-            a = ops.dcn_args(pd, x, om, 32, B, h, w, o, pd.n, ACT_RELU, precise=model.precise, workspace=ws,
-                             in_scale=model._scale(p) if pd.out_scale > 0 else None)
-            self.keep.append(a)
-            if feat_producer:
-                self.feat_producer = a                       # the DCN that writes the feature map (the last node of ida_up)
-            self.inputs[p] = [x]
-            self.step_index[p] = len(self.steps)
-            self.step_flops[p] = 2.0 * B * h * w * pd.n * 9 * pd.c
-            self.add_step((self.lib.cf_dcn_v2_f16x3 if pd.out_scale > 0 else self.lib.cf_dcn_v2_fused, C.byref(a)))
-            return o
-
-        def ida(p, layers, startp, endp, final_out=None, feat=False):
-            """IDAUp.forward (dla.py:518-524).  The projections of one IDA level read maps that all exist when the level
-            starts and do not depend on each other or on the nodes, so with `self.use_lanes` they are issued on a side
-            stream (offset conv + DCN per projection) while the caller's stream runs the node chain
-            upsample+skip -> offset conv -> DCN, waiting for projection j right before it consumes it.  Small
-            batches only: there a single launch cannot fill the chip and the two chains overlap (bit-identical)."""
-            projs = {}
-            if self.use_lanes:
-                self.ctl("rec", 0, ev0 := self.new_event())      # everything the projections read is complete here
-                self.ctl("wait", 1, ev0)
-                self.lane = 1
-                for i in range(startp + 1, endp):
-                    projs[i] = dcn_node(f"{p}.proj_{i - startp}", layers[i])
-                    self.ctl("rec", 1, ev := self.new_event())
-                    projs[i] = (projs[i], ev)
-                self.lane = 0
-            for i in range(startp + 1, endp):
-                j = i - startp
-                if self.use_lanes:
-                    proj, ev = projs[i]
-                    self.ctl("wait", 0, ev)
-                else:
-                    proj = dcn_node(f"{p}.proj_{j}", layers[i])
-                wk, f = pk[f"{p}.up_{j}"]
-                _, h, w, c = proj.shape
-                summed = buf(B, h * f, w * f, c)          # up(proj(x)) + skip, fused
-                self.add_step((self.lib.cf_upsample_dw, proj.data_ptr(), wk.data_ptr(),
-                               layers[i - 1].data_ptr(), summed.data_ptr(), B, h, w, c, f))
-                layers[i] = dcn_node(f"{p}.node_{j}", summed, out=final_out if i == endp - 1 else None,
-                                     feat_producer=feat and i == endp - 1)
-
-        bf = model._heads_bf()                             # fused split-bf16 head launches (False: the exact-fp32 layer-by-layer heads)
-        h4, w4 = H // 4, W // 4
-        self.h4, self.w4 = h4, w4
-        self.in_step = None
-        self.stem = None
-        self.feat_producer = None    # argument block of the DCN whose output is the feature map (set by dcn_node)
-        self.debug = {}
-        if part != "heads":
-            # ---- backbone
-            self.in_step = len(self.steps)
-            self.add_step(None)                            # first step reads the images: patched per call
-            if "base.stem" in pk:
-                # base_layer + level0 + level1 in one launch; the full-resolution maps stay in LDS
-                y0, y1 = None, buf(B, H // 2, W // 2, 32)
-                # ... and the level-2 Tree's 2x2 max-pool of that map (dla.py:96) comes out of the same launch
-                y1p = buf(B, H // 4, W // 4, 32) if model.stem_pool else None
-                if y1p is not None:
-                    pooled[y1.data_ptr()] = y1p
-                stem_layers = ("base.base_layer", "base.level0", "base.level1")
-                self.stem = ops.stem_args(pk["base.stem"], None, y1, shape=(B, 3, H, W), out_pool=y1p,
-                                          in_scales=[model._scale(n) for n in stem_layers])
-                self.keep.append(self.stem)
-                self.hidden.update(stem_layers)              # (the image is the caller's, the two maps stay in LDS)
-                self.step_index["base.stem"] = self.in_step
-                self.step_flops["base.stem"] = 2.0 * B * H * W * (16 * 147 + 16 * 144 + 32 * 144 / 4)
-            else:
-                self.x4 = buf(B, H, W, 4)
-                t, _ = conv("base.base_layer", [self.x4], H, W)
-                y0, _ = conv("base.level0", [t], H, W)
-                y1, _ = conv("base.level1", [y0], H, W)
-            layers = [y0, y1]
-            x = y1
-            for lvl, levels, root in ((2, 1, False), (3, 2, True), (4, 2, True), (5, 1, True)):
-                x = tree(f"base.level{lvl}", levels, x, 2, root)
-                layers.append(x)
-            self.debug = {f"y{i}": t for i, t in enumerate(layers) if t is not None}   # NHWC stage outputs (tests only)
-            # ---- DLA-up + IDA-up neck
-            out = [layers[-1]]
-            for i in range(len(layers) - 2 - 1):
-                ida(f"dla_up.ida_{i}", layers, len(layers) - i - 2, len(layers))
-                out.insert(0, layers[-1])
-            for i, t in enumerate(out):
-                self.debug[f"up{i}"] = t
-            y = out[:3]
-            ida("ida_up", y, 0, 3, final_out=feat, feat=True)
-            feat = y[-1]
-            if bf and model._mx_active:
-                # heads' first layer on fp16 + FP6 (cf_head_fused mx = 1): the 272-byte rows it stages, one pass over the
-                # fp32 feature map of this (sub-)batch
-                if feat_in is None:
-                    feat_in = buf(B, h4, w4, packing.MX_ROW, dtype=torch.uint8)
-                # ... written by the epilogue of the DCN that produces the map (f16x3 kernel, no K split at this size); a
-                # separate pass over the fp32 map only if that kernel is not in use
-                # (the feature map's DCN runs WITHOUT a K split whenever it also writes the heads' rows - the two exclude each
-                #  other - so on maps small enough for the split, <= 2048 pixels per image, the summation order of that one
-                #  layer depends on pack_mx_fused / heads_mx: same arithmetic, rounding differs; DESIGN.md section 4.3)
-                pr = self.feat_producer
-                if pr is not None and pr.out_scale > 0 and pr.N == 64 and pr.N_pad == 64 and bool(model.pack_mx_fused):
-                    pr.out_mx = feat_in.data_ptr()
-                    pr.mx_scale = model._feat_scale
-                    pr.workspace = None
-                else:
-                    self.step_index["feat.pack_mx"] = len(self.steps)
-                    self.add_step((self.lib.cf_pack_feat_mx_scaled, feat.data_ptr(), 64, feat_in.data_ptr(), C.c_long(B * h4 * w4),
-                                   C.c_float(model._feat_scale)))
-            elif bf:
-                # the split-bf16 copy of the feature map the heads read is written by the epilogue of the DCN
-                # that produces it (f16x3 kernel); a separate split pass only if that kernel is not in use
-                if feat_in is None:
-                    feat_in = buf(B, h4, w4, 2, 64, dtype=torch.bfloat16)
-                pr = self.feat_producer
-                if pr is not None and pr.out_scale > 0 and pr.N == 64:
-                    pr.out_split_bf16, pr.split_stride = feat_in.data_ptr(), 64
-                    pr.workspace = None                    # (the split output and a K-split reduction exclude each other)
-                else:
-                    self.add_step((self.lib.cf_split_bf16, feat.data_ptr(), feat_in.data_ptr(), B * h4 * w4, 64, 64, 64))
-            else:
-                feat_in = feat
-        self.feat, self.feat_in = feat, feat_in
-        self.primary, self.radar, self.K = [], False, K
-        self.outs: Dict[str, List] = {}
-        self.tails = {}
-        if part == "trunk":
-            return
-
-        # ---- heads.  Per-call output tensors are patched into these arg blocks (self.outs).
-        primary = [h for h in heads if not (radar and h in SECONDARY_HEADS)]
-        self.primary = primary
-        self.radar = radar
-        M4 = B * h4 * w4
-        if feat is not None:                                # the fp32 feature map both head groups read (as mx / split-bf16 / fp32)
-            self.inputs["heads.primary.0"] = [feat]
-            if radar:
-                self.inputs["heads.secondary.0"] = [feat]
-
-        def hconv(name, srcs, strides, out_c=None, out=None, out_offset=0, act=ACT_RELU):
-            """One hidden head layer of the exact-fp32 heads (model.heads_bf16 = False): fp32 NHWC, cf_conv2d_fused."""
-            pc = pk[name]
-            if out is None:
-                out = buf(B, h4, w4, out_c)
-            stride = out.shape[-1]
-            a = ops.conv_args(pc, srcs, strides, B, h4, w4, out, stride, act, None, 0, LAYOUT_NHWC, None, out_offset, False, 4)
-            self.keep.append(a)
-            self.step_index[name] = len(self.steps)
-            self.step_flops[name] = 2.0 * M4 * pc.n * (pc.kh * pc.kh * sum(int(c) for c in pc.real_cin))
-            self.add_step((self.lib.cf_conv2d_fused, C.byref(a)))
-            return out
-
-        def head_out(h, src, src_stride):
-            act = ACT_SIGMOID_CLAMP if h == "heatmap" else (
-                ACT_RAW_AND_SIGDEPTH if h in ("depth", "depth2") else ACT_NONE)
-            pc = pk[f"heads.{h}.out"]
-            a = ops.conv_args(pc, [src], [src_stride], B, h4, w4, src, 0, act, None, 0,
-                              LAYOUT_NCHW, src if act == ACT_RAW_AND_SIGDEPTH else None, 0, False)
-            self.keep.append(a)
-            self.step_index[f"heads.{h}.out"] = len(self.steps)
-            self.step_flops[f"heads.{h}.out"] = 2.0 * M4 * pc.n * 256
-            self.add_step((self.lib.cf_conv2d_fused, C.byref(a)))
-            self.outs[h] = a
-
-        hs = 256 * len(primary)
-        hid = None if bf else hconv("heads.primary.0", [feat_in], [64], out_c=hs)
-
-        def act_of(h):
-            return ACT_SIGMOID_CLAMP if h == "heatmap" else (
-                ACT_RAW_AND_SIGDEPTH if h in ("depth", "depth2") else ACT_NONE)
-
-        def fused_heads(name, names, srcs, strides, pkname=None):
-            """One cf_head_fused launch: 3x3 + ReLU + tail for sibling heads, hidden never in HBM."""
-            hd = [dict(pk[pkname or name][h], act=act_of(h)) for h in names]
-            f = ops.head_fused_args(srcs, strides, hd[0].get("slots"), hd[0].get("k_pad", 0), B, h4, w4, hd)
-            self.keep.append(f)
-            for n, h in enumerate(names):
-                self.tails[h] = (f.tail, n)
-            self.step_index[name] = len(self.steps)
-            self.step_flops[name] = sum(
-                2.0 * M4 * 256 * (9 * sum(d["real_cin"]) + 256 * len(d["w_hidden"]) + heads[h])
-                for h, d in zip(names, hd))
-            self.add_step((self.lib.cf_head_fused, C.byref(f)))
-
-        fuse_all = bf
-        # Two lanes for the decoder's index kernels (model.heads_lanes, fused heads): behind the primary launch the side stream
-        # runs the decoder's NMS + top-k (handed to decode.py through the heat map tensor, see run()) beside the frustum
-        # path and the secondary launch, instead of alone on the chip behind the last head launch.  (Splitting the primary
-        # launch in two so that the frustum path's top-k could go there as well costs the head launches more than both
-        # top-k passes take: DESIGN.md section 9.)
-        self.peaks_step = None
-        split = fuse_all and bool(model.heads_lanes) and primary[0] == "heatmap"
-        def peaks_lane():
-            """the side lane: starts behind whatever the caller's stream has issued so far, runs the decoder's NMS + top-k"""
-            ev_a = self.new_event()
-            self.ctl("rec", 0, ev_a)
-            self.lane = 1
-            self.ctl("wait", 1, ev_a)
-            self.pk_ws = buf(max(1, self.lib.cf_topk_workspace_bytes_nms(B, heads["heatmap"], h4, w4, K)), dtype=torch.uint8)
-            self.peaks_step = len(self.steps); self.add_step(None)
-            self.ev_peaks = self.new_event()
-            self.ctl("rec", 1, self.ev_peaks)
-            self.lane = 0
-
-        if split:
-            self.use_lanes = True
-            fused_heads("tails.primary", primary, [feat_in], [64])
-            # radar: the lane starts behind the frustum chain (below), not behind the primary launch - its chip-wide NMS pass
-            # beside the chain's slice top-k tripled that kernel's time (41 vs 14 us) on the one path everything waits for
-            # (no frustum chain - MODEL.FRUSTUM = False -: behind the primary launch, as on a camera-only model)
-            if not (frustum and model.peaks_behind_frustum):
-                peaks_lane()
-        elif fuse_all:
-            fused_heads("tails.primary", primary, [feat_in], [64])
-        else:
-            for h in primary:
-                head_out(h, hid, hs)
-        self.frustum = frustum
-        if radar:
-            self.pc_hm4 = None if bf else buf(B, h4, w4, 4)
-            self.pc_hm8 = buf(B, h4, w4, 2, 8, dtype=torch.bfloat16) if bf else None
-            self.topk_step = None
-            if frustum:
-                self.tk_scores = buf(B, K)
-                self.tk_inds = buf(B, K, dtype=torch.int32)
-                self.tk_cls = buf(B, K, dtype=torch.int32)
-                self.tk_ws = buf(max(1, self.lib.cf_topk_workspace_bytes(B, K)), dtype=torch.uint8)
-                # top-k of the raw heat map -> association (pointcloud.py:347-392): cf_topk_frustum (two launches: the merge of the slice
-                # lists runs in the association kernel's prologue) or, model.frustum_fused = False, cf_topk_peaks + cf_frustum_assoc (three)
-                if not model.frustum_fused:
-                    self.topk_step = len(self.steps); self.add_step(None)
-            # (MODEL.FRUSTUM = False: no top-k, no association - the slot holds cf_pc_hm_direct, which normalises the caller's map in
-            #  place and writes the secondary heads' channels-last copies; the secondary launch then depends on nothing the primary wrote)
-            self.frustum_step = len(self.steps); self.add_step(None)
-            if not frustum:
-                self.step_index["pc_hm_direct"] = self.frustum_step
-                self.step_flops["pc_hm_direct"] = 0.0
-            ss = 256 * len(SECONDARY_HEADS)
-            if split and self.peaks_step is None:
-                peaks_lane()
-            if fuse_all:
-                fused_heads("tails.secondary", SECONDARY_HEADS, [feat_in, self.pc_hm8], [64, 8])
-                if split:
-                    self.ctl("wait", 0, self.ev_peaks)
-                return
-            s1 = hconv("heads.secondary.0", [feat_in, self.pc_hm4], [64, 4], out_c=ss)
-            s2 = buf(B, h4, w4, ss)
-            for n, h in enumerate(SECONDARY_HEADS):
-                hconv(f"heads.{h}.2", [s1], [ss], out=s2, out_offset=256 * n)
-                hconv(f"heads.{h}.4", [s2], [ss], out=s1, out_offset=256 * n)
-                head_out(h, s1, ss)
-        elif split:
-            self.ctl("wait", 0, self.ev_peaks)
-
-    # ------------------------------------------------------------------------------------------
-    def add_step(self, step):
-        self.steps.append(step)
-        self.lanes.append(self.lane)
-
-    def ctl(self, op, lane, ev):
-        """Cross-lane ordering: ("rec" | "wait", lane, event id)."""
-        self.steps.append((op, ev))
-        self.lanes.append(lane)
-
-    def new_event(self):
-        self.n_events += 1
-        return self.n_events - 1
-
-    def _launch(self, st):
-        """Issue the plan's steps.  With lanes (and outside a stream capture) a step runs on the caller's stream (lane 0) or
-        on the plan's side stream (lane 1), ordered by the ("rec" | "wait", event) control steps; otherwise everything runs
-        in list order on the caller's stream (the list order is a valid sequential order).  Timed steps (model.time_launch)
-        are bracketed by HIP events recorded on the stream the step runs on."""
-        lanes_on = self.use_lanes and not torch.cuda.is_current_stream_capturing()
-        timed = self.timed
-        if not lanes_on:
-            for i, step in enumerate(self.steps):
-                if isinstance(step[0], str):
-                    continue                                   # one stream: program order is the dependency order
-                ev = timed.get(i) if timed else None
-                if ev is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                rc = step[0](*step[1:], st)
-                if ev is not None:
-                    e1.record()
-                    ev.append((e0, e1))
-                if rc != 0:
-                    _lib.check(rc, step[0].__name__)
-            return
-        cur = torch.cuda.current_stream(self.device)
-        if getattr(self, "_side", None) is None:
-            self._side = _side_streams(self.device, cur.cuda_stream, 1)[0]
-            self._events = [torch.cuda.Event() for _ in range(self.n_events)]
-        streams = (cur, self._side)
-        ptrs = (st, self._side.cuda_stream)
-        for i, (step, lane) in enumerate(zip(self.steps, self.lanes)):
-            op = step[0]
-            if op == "rec":
-                self._events[step[1]].record(streams[lane])
-            elif op == "wait":
-                streams[lane].wait_event(self._events[step[1]])
-            else:
-                ev = timed.get(i) if timed else None
-                if ev is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(streams[lane])
-                rc = op(*step[1:], ptrs[lane])
-                if ev is not None:
-                    e1.record(streams[lane])
-                    ev.append((e0, e1))
-                if rc != 0:
-                    _lib.check(rc, op.__name__)
-        # (every side-lane launch is waited for by a main-lane step that consumes it: the caller's stream is again
-        #  the only one with work in flight when this returns)
-
-    def run_trunk(self, x):
-        """part == "trunk": images of this sub-batch -> its slice of the shared feature buffers (current stream)."""
-        lib = self.lib
-        if self.stem is not None:
-            self.stem.x = x.data_ptr()
-            self.steps[self.in_step] = (lib.cf_stem_fused, C.byref(self.stem))
-        else:
-            self.steps[self.in_step] = (lib.cf_nchw_to_nhwc4, x.data_ptr(), self.x4.data_ptr(), self.B, 3, self.H, self.W)
-        self._launch(_lib.stream_ptr())
-
-    def run(self, model, x, pc_dep, calib, alloc=None):
-        """alloc(c): where a (B, c, h4, w4) output goes (default: a fresh tensor).  part == "heads": `x` is unused
-        (the feature buffers were filled by the trunk plans)."""
-        B, H, W, dev = self.B, self.H, self.W, self.device
-        lib = self.lib
-        st = _lib.stream_ptr()
-        h4, w4 = self.h4, self.w4
-        heads = model.config.heads
-        y = {}
-        new = alloc or (lambda c: torch.empty((B, c, h4, w4), device=dev, dtype=torch.float32))
-        def set_out(h, t, second=False):
-            if h in self.tails:
-                a, n = self.tails[h]
-                (a.out2 if second else a.out)[n] = t.data_ptr()
-            elif second:
-                self.outs[h].out2 = t.data_ptr()
-            else:
-                self.outs[h].out = t.data_ptr()
-
-        for h in self.primary:
-            t = new(heads[h])
-            y[h] = t
-            set_out(h, t)
-        depth_raw = y["depth"]                             # raw logits; "depth" gets the sigmoid form
-        y["depthMap"] = depth_raw
-        y["depth"] = new(1)
-        set_out("depth", y["depth"], second=True)
-        y["calib"] = calib
-        if self.peaks_step is not None:
-            # the decoder's peaks (3x3 NMS + top-K of the heat map, decode.py) are computed on the side lane beside the second
-            # primary launch and travel with the heat map tensor: decode._peaks_and_maps picks them up when K and the
-            # tensor's version still match, and computes them itself otherwise
-            peaks_on = not torch.cuda.is_current_stream_capturing()   # (a captured forward hands out copies of its maps: nothing to carry)
-            if peaks_on:
-                pk_s = torch.empty((B, self.K), device=dev, dtype=torch.float32)
-                pk_i = torch.empty((B, self.K), device=dev, dtype=torch.int32)
-                pk_c = torch.empty((B, self.K), device=dev, dtype=torch.int32)
-                pk_sum = torch.empty(2 * ops.CHECKSUM_PARTS, device=dev, dtype=torch.int64)   # checksum parts of the map the peaks belong to | decode's re-check
-                n_words = B * heads["heatmap"] * h4 * w4
-                self.steps[self.peaks_step] = (_peaks_and_checksum, lib, (y["heatmap"].data_ptr(), B, heads["heatmap"], h4, w4, self.K, 2,
-                                               pk_s.data_ptr(), pk_i.data_ptr(), pk_c.data_ptr(), self.pk_ws.data_ptr()),
-                                               (y["heatmap"].data_ptr(), C.c_long(n_words), pk_sum.data_ptr()))
-            else:
-                self.steps[self.peaks_step] = (_no_launch,)
-        if self.in_step is not None:
-            if self.stem is not None:
-                self.stem.x = x.data_ptr()
-                self.steps[self.in_step] = (lib.cf_stem_fused, C.byref(self.stem))
-            else:
-                self.steps[self.in_step] = (lib.cf_nchw_to_nhwc4, x.data_ptr(), self.x4.data_ptr(), B, 3, H, W)
-        if self.radar and not self.frustum:
-            # base_model.py:69-79 + detectHeads.py:172-190: ONE in-place normalisation of the caller's tensor per forward; pc_hm_in,
-            # pc_hm and pc_hm_out are all channel 0 of that tensor
-            self.steps[self.frustum_step] = (
-                lib.cf_pc_hm_direct, pc_dep.data_ptr(), B, h4, w4, C.c_float(float(model.config.DATASET.MAX_PC_DIST)),
-                _lib.ptr(self.pc_hm4), _lib.ptr(self.pc_hm8))
-            y["pc_hm_in"] = pc_dep[:, :1]
-            y["pc_hm"] = pc_dep[:, 0, :, :].unsqueeze(1)
-            for h in SECONDARY_HEADS:
-                t = new(heads[h])
-                y[h] = t
-                set_out(h, t)
-            y["pc_hm_out"] = pc_dep[:, :1]
-            y["depthMap"] = y["depth2"]                    # raw depth2 logits (detectHeads.py:188-190)
-            y["depth2"] = new(1)
-            set_out("depth2", y["depth2"], second=True)
-        elif self.radar:
-            pc_hm = new(3)
-            if self.topk_step is None:
-                self.steps[self.frustum_step] = (
-                    lib.cf_topk_frustum, y["heatmap"].data_ptr(), heads["heatmap"], self.K, y["depth"].data_ptr(),
-                    y["widthHeight"].data_ptr(), y["dimension"].data_ptr(), y["rotation"].data_ptr(),
-                    calib.data_ptr(), pc_dep.data_ptr(), B, h4, w4,
-                    C.c_float(float(model.config.DATASET.MAX_PC_DIST)), pc_hm.data_ptr(),
-                    _lib.ptr(self.pc_hm4), _lib.ptr(self.pc_hm8), self.tk_scores.data_ptr(), self.tk_inds.data_ptr(),
-                    self.tk_cls.data_ptr(), self.tk_ws.data_ptr())
-            else:
-                self.steps[self.topk_step] = (lib.cf_topk_peaks, y["heatmap"].data_ptr(), B, heads["heatmap"],
-                                              h4, w4, self.K, 0, self.tk_scores.data_ptr(),
-                                              self.tk_inds.data_ptr(), self.tk_cls.data_ptr(),
-                                              self.tk_ws.data_ptr())
-                self.steps[self.frustum_step] = (
-                    lib.cf_frustum_assoc, self.tk_inds.data_ptr(), self.K, y["depth"].data_ptr(),
-                    y["widthHeight"].data_ptr(), y["dimension"].data_ptr(), y["rotation"].data_ptr(),
-                    calib.data_ptr(), pc_dep.data_ptr(), B, h4, w4,
-                    C.c_float(float(model.config.DATASET.MAX_PC_DIST)), pc_hm.data_ptr(),
-                    _lib.ptr(self.pc_hm4), _lib.ptr(self.pc_hm8))
-            y["pc_hm_in"] = pc_dep[:, :1]
-            y["pc_hm"] = pc_hm[:, 0, :, :].unsqueeze(1)
-            for h in SECONDARY_HEADS:
-                t = new(heads[h])
-                y[h] = t
-                set_out(h, t)
-            y["pc_hm_out"] = pc_hm[:, :1]
-            y["depthMap"] = y["depth2"]                    # raw depth2 logits (detectHeads.py:188-190)
-            y["depth2"] = new(1)
-            set_out("depth2", y["depth2"], second=True)
-        self._launch(st)
-        if self.peaks_step is not None and peaks_on:
-            hm = y["heatmap"]
-            # (decode.py re-checks the map's contents against pk_sum[0] on the device before it trusts the peaks)
-            hm._cf_peaks = (self.K, hm.data_ptr(), pk_s, pk_i, pk_c, pk_sum)
-            side = getattr(self, "_side", None)
-            if side is not None:                               # (allocator: these tensors were also used on the side stream)
-                for t in (hm, pk_s, pk_i, pk_c, pk_sum):
-                    t.record_stream(side)
-        return [y]
-
-
-
-def _no_launch(stream):
-    """a plan step that issues nothing (status 0)"""
-    return 0
-
-
-def _peaks_and_checksum(lib, topk_args, sum_args, stream):
-    """the decoder's NMS + top-k of the heat map and the checksum of the bits they were computed from (one plan step)"""
-    rc = lib.cf_topk_peaks(*topk_args, stream)
-    return rc if rc != 0 else lib.cf_checksum64(*sum_args, stream)
-
-
 # ----------------------------------------------------------------------------------- the module
 class DLASeg(nn.Module):
     def __init__(self, num_layers, in_channels, config):
@@ -883,7 +186,7 @@ class DLASeg(nn.Module):
         self._lock = threading.RLock()     # plans (buffers + argument blocks) are built / patched / launched under it
         self.precise = True      # two-level fp32 summation in backbone + neck (see cf_gemm.hip)
         self.conv_f16 = True     # backbone / offset convs: fp32 storage, split-fp16 products (cf_gemm_f16.hip)
-        self.lanes = True        # small batches: the IDA projections on a side stream beside the node chain (_Plan.ida)
+        self.lanes = True        # small batches: the IDA projections on a side stream beside the node chain (plan.py: _Plan._ida)
         self.lanes_max_frames = 10 # ... up to this many 448x800-frame equivalents per single-stream forward (round 6, ms per step with /
                                    # without: bs 5 3.35 / 3.39, 6 4.00 / 4.08, 7 4.23 / 4.31, 8 4.60 / 4.67, 10 5.26 / 5.35, 11 5.69 / 5.67)
         self.streams = 2         # > 1 (and batch >= min_sub_batch * streams): backbone + neck as that many sub-batches on
@@ -901,7 +204,7 @@ class DLASeg(nn.Module):
         self.root_fuse_children = False   # ... also where the Root has further sources (level3.tree2, level4.tree2): same bits, and
                                           # in the two-stream step the two launches are 0.024 ms faster (round 5, 6 of 6 A/B pairs)
         self.heads_lanes = True  # fused heads: the decoder's NMS + top-k on a side stream beside the frustum path and the secondary
-                                 # launch (_Plan heads section), handed to decode.py with the heat map
+                                 # launch (plan.py: _Plan._build_heads), handed to decode.py with the heat map
         self.peaks_behind_frustum = True  # heads_lanes on a radar model: the decoder's lane starts behind the frustum chain instead of
                                           # behind the primary head launch (False: round 5's order; same results)
         self.frustum_fused = True  # radar: top-k of the raw heat map + frustum association as cf_topk_frustum (2 launches, the merge in the
@@ -1410,14 +713,12 @@ class DLASeg(nn.Module):
         h4, w4 = H // 4, W // 4
         cur = torch.cuda.current_stream(dev)
         pool = _side_streams(dev, sid, n)
-        bf = self._heads_bf()
+        spec = feat_operand(self)
+        bf = spec is not None
 
         def heads_plan():
             feat = torch.empty((B, h4, w4, 64), device=dev, dtype=torch.float32)
-            if bf and self._mx_active:
-                feat_in = torch.empty((B, h4, w4, packing.MX_ROW), device=dev, dtype=torch.uint8)
-            else:
-                feat_in = torch.empty((B, h4, w4, 2, 64), device=dev, dtype=torch.bfloat16) if bf else feat
+            feat_in = torch.empty((B, h4, w4, *spec[0]), device=dev, dtype=spec[1]) if bf else feat
             return _Plan(self, B, H, W, dev, part="heads", feat=feat, feat_in=feat_in)
 
         hplan = self._plan((B, H, W, dev, sid, "heads", n), heads_plan, store)
