@@ -62,6 +62,10 @@ class StemArgs(C.Structure):
                 ("out", _f), ("out_pool", _f), ("in_scale", C.c_float * 3)]
 
 
+class StemEarlyArgs(C.Structure):
+    _fields_ = [("stem", StemArgs), ("pc", _f), ("pc_h", C.c_int32), ("pc_w", C.c_int32), ("w_base_radar", _f)]
+
+
 class PackSrc(C.Structure):
     _fields_ = [("channels", C.c_int32), ("stride", C.c_int32), ("c_base", C.c_int32)]
 
@@ -106,6 +110,7 @@ SYMBOLS = {
     "cf_conv3x3_root_f16x3": (_i, [C.POINTER(ConvArgs), C.POINTER(ConvArgs), C.POINTER(C.c_int32), _f]),
     "cf_conv3x3_proj_f16x3": (_i, [C.POINTER(ConvArgs), C.POINTER(C.c_int32), _f]),
     "cf_stem_fused": (_i, [C.POINTER(StemArgs), _f]),
+    "cf_stem_fused_early": (_i, [C.POINTER(StemEarlyArgs), _f]),
     "cf_split_bf16": (_i, [_f, _f, C.c_long, _i, _i, _i, _f]),
     "cf_head_fused": (_i, [C.POINTER(HeadFusedArgs), _f]),
     "cf_pack_feat_mx": (_i, [_f, _i, _f, C.c_long, _f]),

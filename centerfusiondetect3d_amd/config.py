@@ -84,3 +84,15 @@ def centernet_config(input_size=(448, 800)):
     c.MODEL.INPUT_SIZE = tuple(input_size)
     c.MODEL.OUTPUT_SIZE = (input_size[0] // 4, input_size[1] // 4)
     return update_heads(c)
+
+
+def centerfusion_early_config(input_size=(448, 800)):
+    """Early radar fusion (MODEL.FUSION_STRATEGY = 'early'): the radar map rides in the image as channels 3-5 of a six-channel
+    DLA-34 stem; nine heads on the image features, `velocity` and `nuscenes_att` with three hidden layers, no depth2 / rotation2.
+    MODEL.FRUSTUM is not read in this mode (base_model.py:69-79)."""
+    c = _base()
+    c.NAME = "CenterFusion_Early"
+    c.MODEL.FUSION_STRATEGY = "early"
+    c.MODEL.INPUT_SIZE = tuple(input_size)
+    c.MODEL.OUTPUT_SIZE = (input_size[0] // 4, input_size[1] // 4)
+    return update_heads(c)

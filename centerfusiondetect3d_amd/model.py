@@ -54,6 +54,11 @@ def _conv_init(co, ci, k):
     return w
 
 
+def is_early(config):
+    """Early radar fusion (model/model.py:35-40): the radar map rides in the image as channels 3-5, the heads see no radar."""
+    return bool(config.DATASET.RADAR_PC) and config.MODEL.FUSION_STRATEGY == "early"
+
+
 def _param_spec(config) -> List[tuple]:
     """[(name, tensor, is_buffer)] in the reference's registration order."""
     spec = []
@@ -71,7 +76,7 @@ def _param_spec(config) -> List[tuple]:
         spec.append((name + ".running_var", torch.ones(c), True))
         spec.append((name + ".num_batches_tracked", torch.tensor(0, dtype=torch.long), True))
 
-    conv("base.base_layer.0", 16, 3, 7); bn("base.base_layer.1", 16)
+    conv("base.base_layer.0", 16, 6 if is_early(config) else 3, 7); bn("base.base_layer.1", 16)
     conv("base.level0.0", 16, 16, 3); bn("base.level0.1", 16)
     conv("base.level1.0", 32, 16, 3); bn("base.level1.1", 32)
 
@@ -155,20 +160,29 @@ class DLASeg(nn.Module):
         super().__init__()
         if str(num_layers) != "34":
             raise NotImplementedError("only DLA-34 is implemented (the reference ships nothing else)")
-        if in_channels != 3:
-            raise NotImplementedError("early fusion (radar channels in the image) is outside the hot path")
-        if config.MODEL.DLA.NODE != "DeformConv":
-            raise NotImplementedError("MODEL.DLA.NODE must be DeformConv (the only node type that works upstream)")
         if getattr(config.DATASET, "ONE_HOT_PC", False):
             raise NotImplementedError("ONE_HOT_PC is outside the hot path")
+        early = is_early(config)
+        if early and any(h in config.heads for h in ("depth2", "rotation2")):
+            # (the reference derives the heads from the strategy, config/utils.py:69-166; a config whose strategy was switched
+            #  afterwards still lists middle fusion's radar heads, which an early model has no input for)
+            raise NotImplementedError("early fusion with depth2 / rotation2 in config.heads: the heads were derived for middle "
+                                      "fusion - run update_heads(config) after setting MODEL.FUSION_STRATEGY")
+        if in_channels != (6 if early else 3):
+            raise NotImplementedError(f"in_channels={in_channels}: 6 with DATASET.RADAR_PC and MODEL.FUSION_STRATEGY = 'early' "
+                                      "(image + 3 radar channels), 3 otherwise")
+        if config.MODEL.DLA.NODE != "DeformConv":
+            raise NotImplementedError("MODEL.DLA.NODE must be DeformConv (the only node type that works upstream)")
         self.config = config
         self.heads = config.heads
         self.isRadarEnabled = bool(config.DATASET.RADAR_PC)
         self.fusionStrategy = config.MODEL.FUSION_STRATEGY if self.isRadarEnabled else None
-        if self.fusionStrategy not in (None, "middle"):
+        if self.fusionStrategy not in (None, "middle", "early"):
             raise NotImplementedError(f"fusion strategy {self.fusionStrategy!r} is outside the hot path")
+        # early fusion (base_model.py:89-92): the normalised radar map is channels 3-5 of the stem's input; nine image-only heads
+        self.isEarly = early
         # middle fusion with MODEL.FRUSTUM = False: the normalised radar map goes straight to the secondary heads (base_model.py:69-79)
-        self.isFrustumEnabled = self.isRadarEnabled and bool(config.MODEL.FRUSTUM)
+        self.isFrustumEnabled = self.isRadarEnabled and bool(config.MODEL.FRUSTUM) and not early
         try:                                               # dla.py:578-580
             config.defrost()
             config.MODEL.PYRAMID_OUT_SIZE = [config.MODEL.OUTPUT_SIZE]
@@ -309,9 +323,11 @@ class DLASeg(nn.Module):
         if f16 and self.stem_fused:
             folded = [packing.fold_bn(sd[f"base.{n}.0.weight"], None, bn(f"base.{n}.1"))
                       for n in ("base_layer", "level0", "level1")]
-            pk["base.stem"] = packing.pack_stem(*[t for wb in folded for t in wb]).to(device)
+            pack = packing.pack_stem_early if self.isEarly else packing.pack_stem
+            pk["base.stem"] = pack(*[t for wb in folded for t in wb]).to(device)
         else:
-            conv_bn("base.base_layer", "base.base_layer.0.weight", "base.base_layer.1", [Source(3, 4)])
+            # (early fusion: the six-channel image is materialised as 8-channel pixels on these paths - plan.py: _early_input)
+            conv_bn("base.base_layer", "base.base_layer.0.weight", "base.base_layer.1", [Source(6, 8) if self.isEarly else Source(3, 4)])
             conv_bn("base.level0", "base.level0.0.weight", "base.level0.1", [Source(16, 16)])
             conv_bn("base.level1", "base.level1.0.weight", "base.level1.1", [Source(16, 16)], stride=2)
 
@@ -364,7 +380,8 @@ class DLASeg(nn.Module):
         head_conv = {k: list(v) for k, v in self.config.head_conv.items()}
         radar = self.isRadarEnabled and self.fusionStrategy == "middle"
         hp = "detectHead_0"
-        primary = [h for h in heads if not (radar and h in SECONDARY_HEADS)]
+        chained = [h for h in heads if len(head_conv[h]) == 3] if self.isEarly else []   # early: velocity / nuscenes_att, image only
+        primary = [h for h in heads if not (radar and h in SECONDARY_HEADS) and h not in chained]
         for h in heads:
             if any(c != 256 for c in head_conv[h]):
                 raise NotImplementedError("head_conv widths other than 256 are not on the path")
@@ -384,12 +401,13 @@ class DLASeg(nn.Module):
                                          torch.cat([hb(h, 0) for h in primary], 0), [feat_src]).to(device)
             for n, h in enumerate(primary):
                 pk[f"heads.{h}.out"] = pack(hw(h, 2), hb(h, 2), [Source(256, 256 * len(primary), 256 * n)]).to(device)
-            if radar:
-                pk["heads.secondary.0"] = pack(torch.cat([hw(h, 0) for h in SECONDARY_HEADS], 0),
-                                               torch.cat([hb(h, 0) for h in SECONDARY_HEADS], 0),
-                                               [feat_src, pc_src]).to(device)
-                ns = 256 * len(SECONDARY_HEADS)
-                for n, h in enumerate(SECONDARY_HEADS):
+            if radar or chained:
+                sec = SECONDARY_HEADS if radar else chained
+                pk["heads.secondary.0"] = pack(torch.cat([hw(h, 0) for h in sec], 0),
+                                               torch.cat([hb(h, 0) for h in sec], 0),
+                                               [feat_src, pc_src] if radar else [feat_src]).to(device)
+                ns = 256 * len(sec)
+                for n, h in enumerate(sec):
                     for idx in (2, 4):
                         pk[f"heads.{h}.{idx}"] = pack(hw(h, idx), hb(h, idx), [Source(256, ns, 256 * n)]).to(device)
                     pk[f"heads.{h}.out"] = pack(hw(h, 6), hb(h, 6), [Source(256, ns, 256 * n)]).to(device)
@@ -410,7 +428,7 @@ class DLASeg(nn.Module):
             # the mx rows' pre-scale: one for both head groups (they read the same rows)
             fr = [self._ranges[n] for n in ("heads.primary.0", "heads.secondary.0") if self._ranges and n in self._ranges]
             self._feat_scale = ops.in_scale_for(max(fr), self.range_headroom) if (mx and fr) else ops.DEFAULT_IN_SCALE
-            def first(h, srcs):
+            def first(h, srcs, mx=mx):
                 if mx:
                     d = packing.pack_head_first_mx(hw(h, 0), hb(h, 0), pc=len(srcs) == 2, feat_scale=self._feat_scale)
                     return dict(w_first=d["w_first"].to(device), b_first=d["b_first"].to(device), first_scale=d["first_scale"],
@@ -422,6 +440,10 @@ class DLASeg(nn.Module):
             if radar:
                 pk["tails.secondary"] = {h: dict(tail(h, [2, 4], 6), **first(h, [feat_src, pc_src]))
                                          for h in SECONDARY_HEADS}
+            if chained:
+                # three-layer heads on the image features alone: bf16x3 first layers (cf_head_fused has no mx form with hidden layers
+                # and one source), reading the split-bf16 copy of the feature map the plan keeps beside the primary group's mx rows
+                pk["tails.chained"] = {h: dict(tail(h, [2, 4], 6), **first(h, [feat_src], mx=False)) for h in chained}
         self._packed = pk
 
     def _heads_bf(self):
@@ -506,12 +528,12 @@ class DLASeg(nn.Module):
             raise _lib.CfHipError("measure_ranges needs device tensors: the HIP path has no CPU fallback")
         with self._lock, torch.cuda.device(images.device), torch.no_grad():
             with torch.random.fork_rng(devices=[]):            # (the shadow's throw-away initialisation draws random numbers)
-                shadow = DLASeg(34, 3, self.config)
+                shadow = DLASeg(34, 6 if self.isEarly else 3, self.config)
             shadow.load_state_dict(self.state_dict())
             shadow.to(images.device)
             shadow.conv_f16, shadow.heads_bf16, shadow.streams, shadow.lanes, shadow.use_graph = False, False, 1, False, False
             if pc_dep is not None and self.isRadarEnabled and not self.isFrustumEnabled:
-                pc_dep = pc_dep.clone()        # (without frustum the forward normalises pc_dep in place: that one mutation is the real forward's)
+                pc_dep = pc_dep.clone()        # (without frustum / with early fusion the forward normalises pc_dep in place: that one mutation is the real forward's)
             shadow(images, pc_dep=pc_dep, calib=calib)
             r = shadow.activation_ranges()
             del shadow
@@ -605,13 +627,14 @@ class DLASeg(nn.Module):
         dev = x.device
         x = x.float().contiguous()
         if self.isRadarEnabled:
-            if pc_dep is None or calib is None:
+            if pc_dep is None or (calib is None and not self.isEarly):    # (early fusion only hands calib through)
                 raise ValueError("radar model: pc_dep and calib are required")
             if tuple(pc_dep.shape) != (B, 3, H // 4, W // 4):
                 raise ValueError(f"pc_dep must be {(B, 3, H // 4, W // 4)}, got {tuple(pc_dep.shape)}")
             if pc_dep.dtype != torch.float32 or not pc_dep.is_contiguous():
                 raise ValueError("pc_dep must be contiguous float32")
-            calib = calib.reshape(B, 3, 4).float().contiguous()
+            if calib is not None:
+                calib = calib.reshape(B, 3, 4).float().contiguous()
         # One model may be driven from several HIP streams and host threads.  A plan owns its intermediate buffers, so
         # plans are keyed by the stream the call is issued on (two forwards in flight on two streams never share a
         # buffer); building, patching the per-call pointers into the argument blocks and issuing the launches happen
@@ -638,7 +661,7 @@ class DLASeg(nn.Module):
         host's launch rate).  Semantics are those of the eager forward: fresh output tensors every call (copies out
         of the static ones), `pc_hm_in` a view of the CALLER's pc_dep, `calib` the caller's tensor.  MODEL.FRUSTUM = False:
         the graph normalises its static copy of pc_dep; channel 0 is copied back, so the caller's tensor ends up normalised
-        exactly once per call and `pc_hm_in` / `pc_hm` / `pc_hm_out` are views of it, as in the eager forward."""
+        exactly once per call and `pc_hm_in` / `pc_hm` / `pc_hm_out` are views of it, as in the eager forward.  Early fusion: the same copy-back of channel 0; there are no pc_hm outputs."""
         in_place = pc_dep is not None and self.isRadarEnabled and not self.isFrustumEnabled
         key = (B, H, W, dev, sid, "graph", self.streams)
         g = self._graphs.pop(key, None)
@@ -722,6 +745,11 @@ class DLASeg(nn.Module):
             return _Plan(self, B, H, W, dev, part="heads", feat=feat, feat_in=feat_in)
 
         hplan = self._plan((B, H, W, dev, sid, "heads", n), heads_plan, store)
+        if self.isEarly:
+            # early fusion: the in-place normalisation (base_model.py:69-79) once, for the whole batch, on the caller's stream in
+            # front of the forks; each trunk's stem reads its sub-batch's slice of the normalised map
+            _lib.check(_lib.load().cf_pc_hm_direct(pc_dep.data_ptr(), B, h4, w4, float(self.config.DATASET.MAX_PC_DIST), None, None,
+                                                   _lib.stream_ptr()), "cf_pc_hm_direct")
         spans = []
         # model.trunk_on_caller: the LAST trunk is issued on the caller's stream itself (behind the forks of the others), so the
         # heads follow its last launch in stream order and wait for n - 1 events instead of n
@@ -738,7 +766,7 @@ class DLASeg(nn.Module):
                 if self.record_spans:
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record(s)
-                tplan.run_trunk(x[i * k:(i + 1) * k])
+                tplan.run_trunk(x[i * k:(i + 1) * k], pc_dep[i * k:(i + 1) * k] if self.isEarly else None)
                 if self.record_spans:
                     e1.record(s)
                     spans.append((e0, e1))
@@ -815,8 +843,8 @@ _network_factory = {"dla": DLASeg}
 
 
 def getModel(config):
-    """model/model.py:18-44."""
+    """model/model.py:18-44 (early fusion: the three radar channels join the image, model.py:35-40)."""
     arch = config.MODEL.ARCH
     num_layers = arch[arch.find("_") + 1:] if "_" in arch else 0
     arch = arch[:arch.find("_")] if "_" in arch else arch
-    return _network_factory[arch](num_layers, in_channels=3, config=config)
+    return _network_factory[arch](num_layers, in_channels=6 if is_early(config) else 3, config=config)

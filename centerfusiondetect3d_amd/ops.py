@@ -720,11 +720,12 @@ def radar_roi_expand(pc_2d, pc_3d, counts, calib, trans, out_hw, roi_method, wan
     return (pc_dep, keep, xy) if want_aux else pc_dep
 
 
-def stem_args(ps, x, out, shape=None, out_pool=None, in_scales=None) -> _lib.StemArgs:
+def stem_args(ps, x, out, shape=None, out_pool=None, in_scales=None, into=None) -> _lib.StemArgs:
     """x may be None with shape=(B, C, H, W) given: the image pointer is then patched in per call.
     out_pool: optional (B, H/4, W/4, 32) buffer for the 2x2 max-pool of the level1 map.
-    in_scales: activation pre-scales (powers of two) of the image, base_layer's output, level0's output (None = 16 each)."""
-    a = _lib.StemArgs()
+    in_scales: activation pre-scales (powers of two) of the image, base_layer's output, level0's output (None = 16 each).
+    into: fill this block (the `stem` member of a StemEarlyArgs) instead of a new one."""
+    a = _lib.StemArgs() if into is None else into
     B, Cc, H, W = shape if x is None else x.shape
     a.x, a.B, a.C, a.H, a.W = (_lib.ptr(x), B, Cc, H, W)
     a.w_base, a.b_base, a.scale_base = ps.w_base.data_ptr(), ps.b_base.data_ptr(), ps.scale_base
@@ -749,6 +750,32 @@ def stem_fused(ps, x, out=None, out_pool=None):
         out = torch.empty((B, H // 2, W // 2, 32), device=x.device, dtype=torch.float32)
     a = stem_args(ps, x.contiguous(), out, out_pool=out_pool)
     _lib.check(_lib.load().cf_stem_fused(C.byref(a), _lib.stream_ptr()), "cf_stem_fused")
+    return out
+
+
+def stem_early_args(ps, x, pc, out, shape=None, out_pool=None, in_scales=None) -> _lib.StemEarlyArgs:
+    """cf_stem_fused_early's block: stem_args (x: the 3-channel image, may be None with shape given) + the radar map pc
+    (B, 3, H/4, W/4) NCHW fp32 (may be None: patched per call; its size is then taken from `shape`) + the radar fragments."""
+    assert ps.w_base_radar is not None, "weights packed without the radar part (packing.pack_stem_early)"
+    e = _lib.StemEarlyArgs()
+    stem_args(ps, x, out, shape=shape, out_pool=out_pool, in_scales=in_scales, into=e.stem)
+    e.pc = _lib.ptr(pc)
+    e.pc_h, e.pc_w = (e.stem.H // 4, e.stem.W // 4) if pc is None else pc.shape[2:]
+    e.w_base_radar = ps.w_base_radar.data_ptr()
+    return e
+
+
+def stem_fused_early(ps, x, pc, out=None, out_pool=None):
+    """Early radar fusion: images (B, 3, H, W) + radar map (B, 3, H/4, W/4), both fp32 NCHW -> the level1 map of the six-channel
+    stem, (B, H/2, W/2, 32) fp32 NHWC (packing.pack_stem_early); out_pool as in stem_fused.  The map is read, not written."""
+    _need_cuda(x, pc, out_pool)
+    B, Cc, H, W = x.shape
+    if pc.dim() != 4 or pc.shape[0] != B or pc.shape[1] != 3 or pc.dtype != torch.float32:
+        raise _lib.CfHipError(f"stem_fused_early: the radar map must be float32 (B, 3, H/4, W/4), got {tuple(pc.shape)}")
+    if out is None:
+        out = torch.empty((B, H // 2, W // 2, 32), device=x.device, dtype=torch.float32)
+    a = stem_early_args(ps, x.contiguous(), pc.contiguous(), out, out_pool=out_pool)
+    _lib.check(_lib.load().cf_stem_fused_early(C.byref(a), _lib.stream_ptr()), "cf_stem_fused_early")
     return out
 
 

@@ -317,25 +317,19 @@ class PackedStem:
     scale_base: float
     scale_level0: float
     scale_level1: float
+    w_base_radar: Optional[torch.Tensor] = None     # pack_stem_early: base_layer's input channels 3..5 (cf_stem_fused_early)
 
     def to(self, device):
         for k in ("w_base", "b_base", "w_level0", "b_level0", "w_level1", "b_level1"):
             setattr(self, k, getattr(self, k).to(device).contiguous())
+        if self.w_base_radar is not None:
+            self.w_base_radar = self.w_base_radar.to(device).contiguous()
         return self
 
 
-def pack_stem(w_base, b_base, w_l0, b_l0, w_l1, b_l1) -> PackedStem:
-    """Weights of cf_stem_fused (BN already folded) in v_mfma_f32_16x16x32_f16 A-operand order: lane
-    l = 16 kg + row holds the 8 k-values of k group kg.
-      base_layer (16, C<=3, 7, 7): 13 k-steps of 4 taps (49 + 3 padding); a k group = ONE tap with
-        k = [4 channels | the same 4 channels] - variant 0 holds {w_hi, w_hi}, variant 1 {w_lo, 0}, to meet
-        the activations stored as [4 ch hi | 4 ch lo];
-      level0 (16, 16, 3, 3) / level1 (32, 16, 3, 3): 5 k-steps of 2 taps (9 + 1 padding); k group kg =
-        channels 8 (kg & 1) .. +8 of tap 2 ks + (kg >> 1); planes hi, lo; level1 has two 16-row tiles."""
-    assert w_base.shape[0] == 16 and w_base.shape[1] <= 3 and tuple(w_base.shape[2:]) == (7, 7)
-    assert tuple(w_l0.shape) == (16, 16, 3, 3) and tuple(w_l1.shape) == (32, 16, 3, 3)
-    hi, lo, s0 = _f16_split(w_base)
-    cb = w_base.shape[1]
+def _stem_base_fragments(hi, lo):
+    """fp16 hi / lo planes (16, C <= 3, 7, 7) of base_layer's scaled weights -> (13, 2, 64, 8) fp16 fragments (see pack_stem)."""
+    cb = hi.shape[1]
     fb = torch.zeros(13, 2, 64, 8, dtype=torch.float16)
     for ks in range(13):
         for kg in range(4):
@@ -347,6 +341,46 @@ def pack_stem(w_base, b_base, w_l0, b_l0, w_l1, b_l1) -> PackedStem:
             fb[ks, 0, rows, 0:cb] = hi[:, :, ky, kx]
             fb[ks, 0, rows, 4:4 + cb] = hi[:, :, ky, kx]
             fb[ks, 1, rows, 0:cb] = lo[:, :, ky, kx]
+    return fb
+
+
+def unpack_stem_base(fb, channels=3):
+    """Inverse of the lane order (tests, tools): (13, 2, 64, 8) fragments -> (hi, lo) planes (16, channels, 7, 7) as float32."""
+    hi, lo = torch.zeros(16, channels, 7, 7), torch.zeros(16, channels, 7, 7)
+    for tap in range(49):
+        ks, kg = divmod(tap, 4)
+        ky, kx = divmod(tap, 7)
+        rows = slice(16 * kg, 16 * kg + 16)
+        hi[:, :, ky, kx] = fb[ks, 0, rows, 0:channels].float()
+        lo[:, :, ky, kx] = fb[ks, 1, rows, 0:channels].float()
+    return hi, lo
+
+
+def pack_stem(w_base, b_base, w_l0, b_l0, w_l1, b_l1) -> PackedStem:
+    """Weights of cf_stem_fused (BN already folded) in v_mfma_f32_16x16x32_f16 A-operand order: lane
+    l = 16 kg + row holds the 8 k-values of k group kg.
+      base_layer (16, C<=3, 7, 7): 13 k-steps of 4 taps (49 + 3 padding); a k group = ONE tap with
+        k = [4 channels | the same 4 channels] - variant 0 holds {w_hi, w_hi}, variant 1 {w_lo, 0}, to meet
+        the activations stored as [4 ch hi | 4 ch lo];
+      level0 (16, 16, 3, 3) / level1 (32, 16, 3, 3): 5 k-steps of 2 taps (9 + 1 padding); k group kg =
+        channels 8 (kg & 1) .. +8 of tap 2 ks + (kg >> 1); planes hi, lo; level1 has two 16-row tiles."""
+    assert w_base.shape[0] == 16 and w_base.shape[1] <= 3 and tuple(w_base.shape[2:]) == (7, 7)
+    return _pack_stem(w_base, b_base, w_l0, b_l0, w_l1, b_l1)
+
+
+def pack_stem_early(w_base, b_base, w_l0, b_l0, w_l1, b_l1) -> PackedStem:
+    """pack_stem for cf_stem_fused_early: base_layer (16, 6, 7, 7) = [image 0-2 | radar 3-5] (fusionModules.py:18-35).  ONE 2^s for
+    all six channels (both parts sum into the same accumulators); `w_base` holds channels 0-2 and `w_base_radar` channels 3-5 as
+    13 k-steps each, in the same lane order.  With all-zero radar weights w_base and scale_base are pack_stem's of the image part."""
+    assert tuple(w_base.shape) == (16, 6, 7, 7)
+    return _pack_stem(w_base, b_base, w_l0, b_l0, w_l1, b_l1)
+
+
+def _pack_stem(w_base, b_base, w_l0, b_l0, w_l1, b_l1) -> PackedStem:
+    assert tuple(w_l0.shape) == (16, 16, 3, 3) and tuple(w_l1.shape) == (32, 16, 3, 3)
+    hi, lo, s0 = _f16_split(w_base)
+    fb = _stem_base_fragments(hi[:, :3], lo[:, :3])
+    fr = _stem_base_fragments(hi[:, 3:], lo[:, 3:]) if w_base.shape[1] > 3 else None
 
     def frag3(w):
         h, l, s = _f16_split(w)
@@ -368,7 +402,7 @@ def pack_stem(w_base, b_base, w_l0, b_l0, w_l1, b_l1) -> PackedStem:
     f0, s1 = frag3(w_l0)
     f1, s2 = frag3(w_l1)
     return PackedStem(fb, b_base.float().clone(), f0[0].contiguous(), b_l0.float().clone(), f1, b_l1.float().clone(),
-                      2.0 ** -(s0 + 4), 2.0 ** -(s1 + 4), 2.0 ** -(s2 + 4))
+                      2.0 ** -(s0 + 4), 2.0 ** -(s1 + 4), 2.0 ** -(s2 + 4), fr)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -59,6 +59,9 @@ class _Plan:
         # trunk: the per-call input step, the fused stem's argument block or the NHWC copy of the images, the argument block
         # of the DCN whose output is the feature map (set by _dcn_node), the max-pools already issued (data_ptr -> output)
         self.in_step = self.stem = self.x4 = self.feat_producer = None
+        # early fusion: the plan's model is one; the step that normalises the caller's radar map (part "all": in front of the stem);
+        # the three-hidden-layer heads on the image features (their own launch); their split-bf16 operand where the primary group reads mx rows
+        self.early, self.direct_step, self.chained, self.feat_bf = bool(model.isEarly), None, [], None
         self._pooled = {}
         # heads: per-call output tensors are patched into the arg blocks in `outs` / `tails`; the other steps patched per
         # call; the radar maps the secondary heads read; the frustum chain's top-k; the decoder's peaks lane
@@ -243,6 +246,10 @@ class _Plan:
 
     def _build_trunk(self):
         m, B, H, W, pk = self._m, self.B, self.H, self.W, self._pk
+        if self.early and self.part == "all":
+            # base_model.py:69-79: the caller's radar map is normalised in place BEFORE the stem reads it (cf_pc_hm_direct without its
+            # channels-last outputs; patched per call).  The split forward does this once for the whole batch (DLASeg._forward_concurrent)
+            self.direct_step = self._add("pc_hm_direct", 0.0, None)
         # ---- backbone.  The first step reads the images: patched per call (_patch_input)
         if "base.stem" in pk:
             # base_layer + level0 + level1 in one launch; the full-resolution maps stay in LDS
@@ -252,13 +259,18 @@ class _Plan:
             if y1p is not None:
                 self._pooled[y1.data_ptr()] = y1p
             stem_layers = ("base.base_layer", "base.level0", "base.level1")
-            self.stem = ops.stem_args(pk["base.stem"], None, y1, shape=(B, 3, H, W), out_pool=y1p,
-                                      in_scales=[m._scale(n) for n in stem_layers])
+            kw = dict(shape=(B, 3, H, W), out_pool=y1p, in_scales=[m._scale(n) for n in stem_layers])
+            self.stem = ops.stem_early_args(pk["base.stem"], None, None, y1, **kw) if self.early else \
+                ops.stem_args(pk["base.stem"], None, y1, **kw)
             self.hidden.update(stem_layers)              # (the image is the caller's, the two maps stay in LDS)
-            self.in_step = self._add("base.stem", 2.0 * B * H * W * (16 * 147 + 16 * 144 + 32 * 144 / 4), None, self.stem)
+            k_base = 16 * 49 * (6 if self.early else 3)
+            self.in_step = self._add("base.stem", 2.0 * B * H * W * (k_base + 16 * 144 + 32 * 144 / 4), None, self.stem)
         else:
             self.in_step = self._slot()
-            self.x4 = self._buf(B, H, W, 4)
+            # (early fusion: [image 0-2 | radar 3-5 | 0 0] per pixel - the six-channel image exists only on these exact-fp32 paths)
+            self.x4 = self._buf(B, H, W, 8 if self.early else 4)
+            if self.early:
+                self.x4.zero_()
             t = self._conv("base.base_layer", [self.x4], H, W)
             y0 = self._conv("base.level0", [t], H, W)
             y1 = self._conv("base.level1", [y0], H, W)
@@ -344,14 +356,35 @@ class _Plan:
         self.ctl("rec", 1, self.ev_peaks)
         self.lane = 0
 
+    def _chained_heads(self, bf, feat, feat_in):
+        """Early fusion: `nuscenes_att` and `velocity` (three hidden layers, detectHeads.py:59-98) on the 64 image channels alone - ONE
+        further cf_head_fused launch, n_src = 1, first layers bf16x3 (the library has no mx form with hidden layers and one source).
+        Where the primary group reads mx rows, the split-bf16 operand is written here from the fp32 map (one pass, whole batch)."""
+        B, h4, w4, chained = self.B, self.h4, self.w4, self.chained
+        if bf:
+            src = feat_in
+            if self._m._mx_active:
+                src = self.feat_bf = self._buf(B, h4, w4, 2, 64, dtype=torch.bfloat16)
+                self._add("feat.split_bf16", None, (self.lib.cf_split_bf16, feat.data_ptr(), src.data_ptr(), C.c_long(B * h4 * w4), 64, 64, 64))
+            self._fused_heads("tails.chained", chained, [src], [64])
+            return
+        ss = 256 * len(chained)                    # (the fp32 chain, as for the secondary heads of middle fusion)
+        s1 = self._hconv("heads.secondary.0", [feat_in], [64], out_c=ss)
+        s2 = self._buf(B, h4, w4, ss)
+        for n, h in enumerate(chained):
+            self._hconv(f"heads.{h}.2", [s1], [ss], out=s2, out_offset=256 * n)
+            self._hconv(f"heads.{h}.4", [s2], [ss], out=s1, out_offset=256 * n)
+            self._head_out(h, s1, ss)
+
     def _build_heads(self):
         m, B, h4, w4, K = self._m, self.B, self.h4, self.w4, self.K
         feat, feat_in = self.feat, self.feat_in
         radar = m.isRadarEnabled and m.fusionStrategy == "middle"
         frustum = radar and m.isFrustumEnabled     # False on a radar model: the radar map itself is pc_hm (base_model.py:69-79)
         bf = m._heads_bf()                         # fused split-bf16 head launches (False: the exact-fp32 layer-by-layer heads)
-        primary = [h for h in m.config.heads if not (radar and h in SECONDARY_HEADS)]
-        self.primary, self.radar, self.frustum = primary, radar, frustum
+        chained = [h for h in m.config.heads if len(m.config.head_conv[h]) == 3] if self.early else []
+        primary = [h for h in m.config.heads if not (radar and h in SECONDARY_HEADS) and h not in chained]
+        self.primary, self.radar, self.frustum, self.chained = primary, radar, frustum, chained
         if feat is not None:                                # the fp32 feature map both head groups read (as mx / split-bf16 / fp32)
             self.inputs["heads.primary.0"] = [feat]
             if radar:
@@ -376,6 +409,8 @@ class _Plan:
             hid = self._hconv("heads.primary.0", [feat_in], [64], out_c=hs)
             for h in primary:
                 self._head_out(h, hid, hs)
+        if chained:
+            self._chained_heads(bf, feat, feat_in)
         if radar:
             self.pc_hm4 = None if bf else self._buf(B, h4, w4, 4)
             self.pc_hm8 = self._buf(B, h4, w4, 2, 8, dtype=torch.bfloat16) if bf else None
@@ -468,17 +503,23 @@ class _Plan:
         # (every side-lane launch is waited for by a main-lane step that consumes it: the caller's stream is again
         #  the only one with work in flight when this returns)
 
-    def _patch_input(self, x):
-        """the trunk's first step reads this call's images"""
-        if self.stem is not None:
+    def _patch_input(self, x, pc=None):
+        """the trunk's first step reads this call's images (early fusion: and this call's normalised radar map `pc`)"""
+        if self.early and self.stem is not None:
+            self.stem.stem.x, self.stem.pc = x.data_ptr(), pc.data_ptr()
+            self.steps[self.in_step] = (self.lib.cf_stem_fused_early, C.byref(self.stem))
+        elif self.early:
+            self.steps[self.in_step] = (_early_input, x, pc, self.x4)
+        elif self.stem is not None:
             self.stem.x = x.data_ptr()
             self.steps[self.in_step] = (self.lib.cf_stem_fused, C.byref(self.stem))
         else:
             self.steps[self.in_step] = (self.lib.cf_nchw_to_nhwc4, x.data_ptr(), self.x4.data_ptr(), self.B, 3, self.H, self.W)
 
-    def run_trunk(self, x):
-        """part == "trunk": images of this sub-batch -> its slice of the shared feature buffers (current stream)."""
-        self._patch_input(x)
+    def run_trunk(self, x, pc=None):
+        """part == "trunk": images of this sub-batch -> its slice of the shared feature buffers (current stream).
+        pc (early fusion): the sub-batch's slice of the ALREADY normalised radar map."""
+        self._patch_input(x, pc)
         self._launch(_lib.stream_ptr())
 
     def _radar_outputs(self, y, out, heads, pc_dep, pc_hm):
@@ -514,7 +555,7 @@ class _Plan:
                 self.outs[h].out = t.data_ptr()
             return t
 
-        for h in self.primary:
+        for h in self.primary + self.chained:              # (early fusion: nuscenes_att, velocity behind the seven - the reference's order)
             y[h] = out(h, heads[h])
         depth_raw = y["depth"]                             # raw logits; "depth" gets the sigmoid form.  (Held until the launches are
         y["depthMap"] = depth_raw                          #  issued: a radar model hands out depth2's logits as depthMap instead)
@@ -537,8 +578,11 @@ class _Plan:
                                                (hm.data_ptr(), C.c_long(n_words), pk_sum.data_ptr()))
             else:
                 self.steps[self.peaks_step] = (_no_launch,)
+        if self.direct_step is not None:
+            self.steps[self.direct_step] = (lib.cf_pc_hm_direct, pc_dep.data_ptr(), B, h4, w4,
+                                            C.c_float(float(model.config.DATASET.MAX_PC_DIST)), None, None)
         if self.in_step is not None:
-            self._patch_input(x)
+            self._patch_input(x, pc_dep)
         if self.radar:
             max_dist = C.c_float(float(model.config.DATASET.MAX_PC_DIST))
             maps = (_lib.ptr(self.pc_hm4), _lib.ptr(self.pc_hm8))
@@ -566,6 +610,15 @@ class _Plan:
                 for t in (hm, pk_s, pk_i, pk_c, pk_sum):
                     t.record_stream(self._side)
         return [y]
+
+
+def _early_input(x, pc, x8, stream):
+    """Early fusion on the exact-fp32 paths (conv_f16 / stem_fused off, the range guards' shadow model): the six-channel image of
+    fusionModules.py:18-35 as 8-channel pixels, [image | radar map nearest-upsampled x4 | 0 0] (channels 6, 7 stay zero).  torch
+    ops on the current stream - the stream every trunk is issued on; off the hot path."""
+    x8[..., :3].copy_(x.permute(0, 2, 3, 1))
+    x8[..., 3:6].copy_(pc.permute(0, 2, 3, 1).repeat_interleave(4, dim=1).repeat_interleave(4, dim=2))
+    return 0
 
 
 def _no_launch(stream):

@@ -107,6 +107,23 @@ typedef struct cf_stem_args {
 } cf_stem_args;
 int cf_stem_fused(const cf_stem_args* a, void* stream);
 
+/* cf_stem_fused_early: cf_stem_fused for EARLY radar fusion (MODEL.FUSION_STRATEGY = "early"): base_layer has six input channels,
+ * [image 0-2 | radar map 3-5], the radar map nearest-upsampled x4 from the output size to the image size.  replaces
+ * model/networks/fusionModules.py:18-35 (ConcateCombiner: F.interpolate + torch.cat) + model/networks/dla.py:250-262 (the stem
+ * on the six-channel image).  The six-channel image is never written: a workgroup reads the map at (y >> 2, x >> 2) into a second
+ * plane of its LDS patch and runs the radar taps as 13 further k-steps into the base layer's accumulators, behind the image's
+ * (with all-zero radar weights the outputs are cf_stem_fused's, bit for bit).  Everything behind base_layer is cf_stem_fused.
+ * `stem` is that entry point's block (x: the image, C <= 3; in_scale[0] pre-scales the radar values too: |v| * in_scale[0] above
+ * 65504 is clamped); w_base / w_base_radar / scale_base come from packing.pack_stem_early (ONE 2^s for all six channels).
+ * H and W must be multiples of 4 and the map exactly (H/4, W/4): anything else returns CF_EINVAL.  (added under ABI 7) */
+typedef struct cf_stem_early_args {
+  cf_stem_args stem;
+  const float* pc;                /* radar map, fp32 NCHW (B, 3, pc_h, pc_w): read only                */
+  int32_t pc_h, pc_w;             /* must be H / 4, W / 4                                              */
+  const void* w_base_radar;       /* [13 k-steps][2][64 lanes][8 f16]: w_base's layout, channels 3-5   */
+} cf_stem_early_args;
+int cf_stem_fused_early(const cf_stem_early_args* a, void* stream);
+
 /* cf_conv2d_f16x3: cf_conv2d_fused semantics (fp32 NHWC sources / residual / output, bias, ReLU) with
  * the products evaluated on the f16 MFMA pipe from split operands (x = hi + lo fp16 after a
  * power-of-two scale): fp32-level accuracy at ~3x the fp32-MFMA rate (cf_gemm_f16.hip).  Differences
