@@ -35,6 +35,7 @@ class DcnArgs(C.Structure):
 
 
 CF_MAX_HEADS = 12
+CF_DEPTH_MAPS_MAX = 8
 
 
 class HeadTailArgs(C.Structure):
@@ -140,6 +141,9 @@ SYMBOLS = {
     "cf_decode_gather": (_i, [C.POINTER(DecodeArgs), _f]),
     "cf_post_process": (_i, [_f, _f, _f, _i, _i, _i, _i, _f, _f]),
     "cf_decode_post": (_i, [C.POINTER(DecodeArgs), _f, _f, _f, _f]),
+    "cf_decode_gather_unc": (_i, [C.POINTER(DecodeArgs), _f, _f]),
+    "cf_decode_post_unc": (_i, [C.POINTER(DecodeArgs), _f, _f, _f, _f, _f]),
+    "cf_depth_maps": (_i, [C.POINTER(_f), C.POINTER(C.c_long), _i, _i, _i, _i, _f, _f]),
     "cf_serialize_nuscenes": (_i, [C.POINTER(SerializeArgs), _f]),
     "cf_serialize_max_candidates": (_i, []),
     "cf_spin_us": (_i, [_i, _f]),

@@ -857,13 +857,17 @@ __global__ __launch_bounds__(PD_THREADS) void pc_hm_direct_kernel(float* __restr
 // ---------------------------------------------------------------------------------------------
 // Detection gather (model/decode.py:40-41, 60-64, 132-172)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void decode_row(const cf_decode_args& a, int t, float* o) {
+// `unc`: the (B,1,H,W) map of the `uncertainty` head or NULL.  With it the score WRITTEN to the row is
+// score * exp(-exp(u)) at the peak pixel (model/decode.py:80-85, precise expf); a.scores is only read, so the
+// peak buffers the forward may share between decodes keep the raw scores, and the row order stays the top-K's.
+__device__ __forceinline__ void decode_row(const cf_decode_args& a, const float* __restrict__ unc, int t, float* o) {
   const int b = t / a.K;
   const int HW = a.H * a.W;
   const int pix = a.inds[t];
   const int yi = pix / a.W, xi = pix - yi * a.W;
   const float xn = (float)xi / (float)a.W, yn = (float)yi / (float)a.H;
-  o[0] = a.scores[t];
+  const float score = a.scores[t];
+  o[0] = unc ? score * expf(-expf(unc[(size_t)b * HW + pix])) : score;
   o[1] = (float)a.classes[t];
   o[2] = xn;
   o[3] = yn;
@@ -903,10 +907,10 @@ __device__ __forceinline__ void decode_row(const cf_decode_args& a, int t, float
   gather(a.depth, 1, 32, 1.0f, 1.0f);
 }
 
-__global__ void decode_gather_kernel(cf_decode_args a) {
+__global__ void decode_gather_kernel(cf_decode_args a, const float* __restrict__ unc) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= a.B * a.K) return;
-  decode_row(a, t, a.det + (size_t)t * 33);
+  decode_row(a, unc, t, a.det + (size_t)t * 33);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -983,18 +987,101 @@ __global__ void post_process_kernel(const float* __restrict__ det, const float* 
 // (model/decode.py:10-174 -> utils/postProcess.py:13-85); `a.det` may be NULL when only the final rows
 // are wanted.  Same arithmetic as the two kernels above (this file is built without FMA contraction),
 // so the fused rows equal cf_decode_gather + cf_post_process bit for bit.
-__global__ void decode_post_kernel(cf_decode_args a, const float* __restrict__ calib,
+__global__ void decode_post_kernel(cf_decode_args a, const float* __restrict__ unc, const float* __restrict__ calib,
                                    const float* __restrict__ tinv, float* __restrict__ post) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= a.B * a.K) return;
   float d[33];
-  decode_row(a, t, d);
+  decode_row(a, unc, t, d);
   if (a.det) {
     float* o = a.det + (size_t)t * 33;
 #pragma unroll
     for (int i = 0; i < 33; ++i) o[i] = d[i];
   }
   post_row(d, calib + (size_t)(t / a.K) * 12, tinv, (float)a.out_w, (float)a.out_h, post + (size_t)t * 54);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Normalised uint8 depth maps of Detector.post_process (detector.py:381-393), all maps of a batch in one launch:
+// one workgroup per (image, map).  Pass 1: min / max over the image's H*W values, row 0 and column 0 of IMAGE 0 read
+// as 0 (the reference's `depthmap[0, 0] = 0; depthmap[0, :, 0] = 0` indexes the batch, not the map: kept); wave
+// reduction, then LDS across the waves.  Pass 2 (the map is in L2 by then): ((x - min) / (max - min)) * 255 truncated,
+// each operation rounded on its own (this file is built without FMA contraction; the division is IEEE), which is
+// numpy's result bit for bit.  A flat image gives 0 / 0: defined as 0 here (numpy's cast of NaN is not defined).
+// V = 4: W % 4 == 0 and 16-byte-aligned maps - float4 loads, one 4-byte store per lane; V = 1: any shape.
+// ---------------------------------------------------------------------------------------------
+#define DM_THREADS 1024
+struct DepthMapPtrs {
+  const float* p[CF_DEPTH_MAPS_MAX];
+  long stride[CF_DEPTH_MAPS_MAX];   // floats between two images of map m (H*W, or more for a channel view)
+};
+
+__device__ __forceinline__ unsigned char depth_u8(float x, float lo, float range) {
+  const float f = ((x - lo) / range) * 255.0f;
+  return f == f ? (unsigned char)(int)f : (unsigned char)0;
+}
+
+template <int V>
+__global__ __launch_bounds__(DM_THREADS) void depth_maps_kernel(DepthMapPtrs maps, int B, int H, int W,
+                                                                unsigned char* __restrict__ out) {
+  const int b = blockIdx.x, m = blockIdx.y;
+  const int HW = H * W, n = HW / V;
+  const float* __restrict__ x = maps.p[m] + (size_t)b * maps.stride[m];
+  unsigned char* __restrict__ o = out + ((size_t)m * B + b) * HW;
+  const bool edge = b == 0;
+  // element i of the image with the reference's zeroing applied (V = 4: a vector starts a row only at its lane 0)
+  auto load = [&](int i, float* v) {
+    if (V == 4) {
+      const f32x4 q = reinterpret_cast<const f32x4*>(x)[i];
+      const int e = i * 4;
+      const bool row0 = edge && e < W;
+      v[0] = (row0 || (edge && e % W == 0)) ? 0.0f : q[0];
+      v[1] = row0 ? 0.0f : q[1];
+      v[2] = row0 ? 0.0f : q[2];
+      v[3] = row0 ? 0.0f : q[3];
+    } else {
+      const float q = x[i];
+      v[0] = (edge && (i < W || i % W == 0)) ? 0.0f : q;
+    }
+  };
+  float lo = INFINITY, hi = -INFINITY;
+  for (int i = threadIdx.x; i < n; i += DM_THREADS) {
+    float v[V];
+    load(i, v);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      lo = fminf(lo, v[j]);
+      hi = fmaxf(hi, v[j]);
+    }
+  }
+  for (int s = 32; s > 0; s >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, s, 64));
+    hi = fmaxf(hi, __shfl_xor(hi, s, 64));
+  }
+  __shared__ float red[2][DM_THREADS / 64];
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = lo;
+    red[1][threadIdx.x >> 6] = hi;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < DM_THREADS / 64; ++w) {
+    lo = fminf(lo, red[0][w]);
+    hi = fmaxf(hi, red[1][w]);
+  }
+  const float range = hi - lo;
+  for (int i = threadIdx.x; i < n; i += DM_THREADS) {
+    float v[V];
+    load(i, v);
+    if (V == 4) {
+      const unsigned int packed = (unsigned int)depth_u8(v[0], lo, range) | ((unsigned int)depth_u8(v[1], lo, range) << 8) |
+                                  ((unsigned int)depth_u8(v[2], lo, range) << 16) |
+                                  ((unsigned int)depth_u8(v[3], lo, range) << 24);
+      reinterpret_cast<unsigned int*>(o)[i] = packed;
+    } else {
+      o[i] = depth_u8(v[0], lo, range);
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1590,12 +1677,22 @@ extern "C" int cf_pc_hm_direct(float* pc_dep, int B, int H, int W, float max_pc_
   return cf_check_launch("cf_pc_hm_direct");
 }
 
-extern "C" int cf_decode_gather(const cf_decode_args* a, void* stream) {
-  CF_REQUIRE(a && a->scores && a->inds && a->classes && a->det, "cf_decode_gather: null buffer");
-  CF_REQUIRE(a->B > 0 && a->K > 0 && a->H > 0 && a->W > 0, "cf_decode_gather: bad geometry");
+// (one launcher for both forms: `unc` NULL = the plain decode)
+static int decode_gather_launch(const char* who, const cf_decode_args* a, const float* unc, void* stream) {
+  CF_REQUIRE(a && a->scores && a->inds && a->classes && a->det, "%s: null buffer", who);
+  CF_REQUIRE(a->B > 0 && a->K > 0 && a->H > 0 && a->W > 0, "%s: bad geometry", who);
   const int n = a->B * a->K;
-  hipLaunchKernelGGL(decode_gather_kernel, dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, *a);
-  return cf_check_launch("cf_decode_gather");
+  hipLaunchKernelGGL(decode_gather_kernel, dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, *a, unc);
+  return cf_check_launch(who);
+}
+
+extern "C" int cf_decode_gather(const cf_decode_args* a, void* stream) {
+  return decode_gather_launch("cf_decode_gather", a, nullptr, stream);
+}
+
+extern "C" int cf_decode_gather_unc(const cf_decode_args* a, const float* uncertainty, void* stream) {
+  CF_REQUIRE(uncertainty, "cf_decode_gather_unc: null uncertainty map");
+  return decode_gather_launch("cf_decode_gather_unc", a, uncertainty, stream);
 }
 
 extern "C" int cf_post_process(const float* det, const float* calib, const float* trans_inv, int B, int K,
@@ -1608,15 +1705,47 @@ extern "C" int cf_post_process(const float* det, const float* calib, const float
   return cf_check_launch("cf_post_process");
 }
 
+static int decode_post_launch(const char* who, const cf_decode_args* a, const float* unc, const float* calib,
+                              const float* trans_inv, float* post, void* stream) {
+  CF_REQUIRE(a && a->scores && a->inds && a->classes && calib && trans_inv && post, "%s: null buffer", who);
+  CF_REQUIRE(a->B > 0 && a->K > 0 && a->H > 0 && a->W > 0 && a->out_h > 0 && a->out_w > 0, "%s: bad geometry", who);
+  const int n = a->B * a->K;
+  hipLaunchKernelGGL(decode_post_kernel, dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, *a, unc, calib,
+                     trans_inv, post);
+  return cf_check_launch(who);
+}
+
 extern "C" int cf_decode_post(const cf_decode_args* a, const float* calib, const float* trans_inv, float* post,
                              void* stream) {
-  CF_REQUIRE(a && a->scores && a->inds && a->classes && calib && trans_inv && post, "cf_decode_post: null buffer");
-  CF_REQUIRE(a->B > 0 && a->K > 0 && a->H > 0 && a->W > 0 && a->out_h > 0 && a->out_w > 0,
-             "cf_decode_post: bad geometry");
-  const int n = a->B * a->K;
-  hipLaunchKernelGGL(decode_post_kernel, dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, *a, calib,
-                     trans_inv, post);
-  return cf_check_launch("cf_decode_post");
+  return decode_post_launch("cf_decode_post", a, nullptr, calib, trans_inv, post, stream);
+}
+
+extern "C" int cf_decode_post_unc(const cf_decode_args* a, const float* uncertainty, const float* calib,
+                                 const float* trans_inv, float* post, void* stream) {
+  CF_REQUIRE(uncertainty, "cf_decode_post_unc: null uncertainty map");
+  return decode_post_launch("cf_decode_post_unc", a, uncertainty, calib, trans_inv, post, stream);
+}
+
+extern "C" int cf_depth_maps(const float* const* maps, const long* batch_strides, int n_maps, int B, int H, int W,
+                             uint8_t* out, void* stream) {
+  CF_REQUIRE(maps, "cf_depth_maps: null maps");
+  CF_REQUIRE(out, "cf_depth_maps: null out");
+  CF_REQUIRE(n_maps >= 1 && n_maps <= CF_DEPTH_MAPS_MAX, "cf_depth_maps: n_maps=%d (1..%d)", n_maps, CF_DEPTH_MAPS_MAX);
+  CF_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (long)H * W <= (1L << 30), "cf_depth_maps: bad geometry");
+  DepthMapPtrs p = {};
+  bool wide = W % 4 == 0 && (uintptr_t)out % 4 == 0;
+  for (int m = 0; m < n_maps; ++m) {
+    CF_REQUIRE(maps[m], "cf_depth_maps: null maps[%d]", m);
+    p.p[m] = maps[m];
+    p.stride[m] = batch_strides ? batch_strides[m] : (long)H * W;
+    CF_REQUIRE(p.stride[m] >= (long)H * W, "cf_depth_maps: batch_strides[%d]=%ld < H*W", m, p.stride[m]);
+    wide = wide && (uintptr_t)maps[m] % 16 == 0 && p.stride[m] % 4 == 0;
+  }
+  if (wide)
+    hipLaunchKernelGGL(depth_maps_kernel<4>, dim3(B, n_maps), dim3(DM_THREADS), 0, (hipStream_t)stream, p, B, H, W, out);
+  else
+    hipLaunchKernelGGL(depth_maps_kernel<1>, dim3(B, n_maps), dim3(DM_THREADS), 0, (hipStream_t)stream, p, B, H, W, out);
+  return cf_check_launch("cf_depth_maps");
 }
 
 extern "C" int cf_serialize_nuscenes(const cf_serialize_args* a, void* stream) {

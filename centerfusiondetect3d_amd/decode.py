@@ -1,7 +1,8 @@
 """Drop-in for the reference's model/decode.py:10-174 (`fusionDecode`) on the HIP path.
 
 NMS + top-k run in one kernel over the NCHW heat map (cf_topk_peaks with nms=1) and the ten
-per-head gathers + box arithmetic in a second one (cf_decode_gather) that reads the K peak pixels
+per-head gathers + box arithmetic in a second one (cf_decode_gather; with an `uncertainty` head in the outputs
+cf_decode_gather_unc, which also weights the scores: decode.py:80-85) that reads the K peak pixels
 straight from the NCHW maps - the reference's ten full-map permute().contiguous() copies
 (model/utils.py:69-71) do not exist here.  Order among equal scores: (class asc, pixel asc).
 """
@@ -23,8 +24,6 @@ def _peaks_and_maps(outputs, K):
     out = outputs[0]
     if "heatmap" not in out:
         return None
-    if "uncertainty" in out:
-        raise NotImplementedError("uncertainty head (TRAIN.UNCERTAINTY_LOSS) is outside the hot path")
     heat = out["heatmap"]
     _, _, H, W = heat.shape
     # The forward may have computed exactly these peaks already, beside its own launches (plan._Plan.run: the heat map tensor
@@ -55,7 +54,10 @@ def _peaks_and_maps(outputs, K):
                       ("depth", "depth")):
         if maps[key] is not None:
             present.append(name)
-    return scores, inds, classes, maps, H, W, present
+    # `uncertainty` (TRAIN.UNCERTAINTY_LOSS): the gather launch multiplies the score it WRITES by exp(-exp(u)) at the peak
+    # (model/decode.py:80-85).  `scores` may be the buffer the forward attached to the heat map, shared by every later decode
+    # of that tensor, so it is only ever read: a second decode weights the same raw scores again.
+    return scores, inds, classes, maps, H, W, present, out.get("uncertainty")
 
 
 def decode_packed(outputs, outputSize=(112, 200), K=100, norm2d=False):
@@ -64,8 +66,8 @@ def decode_packed(outputs, outputSize=(112, 200), K=100, norm2d=False):
     r = _peaks_and_maps(outputs, K)
     if r is None:
         return None, []
-    scores, inds, classes, maps, H, W, present = r
-    det = ops.decode_gather(scores, inds, classes, maps, H, W, outputSize, norm2d)
+    scores, inds, classes, maps, H, W, present, unc = r
+    det = ops.decode_gather(scores, inds, classes, maps, H, W, outputSize, norm2d, uncertainty=unc)
     return det, present
 
 
@@ -77,12 +79,12 @@ def decode_post_packed(outputs, calibs, trans_inv, outputSize=(112, 200), K=100,
     r = _peaks_and_maps(outputs, K)
     if r is None:
         raise ValueError("decode_post_packed: outputs hold no heatmap")
-    scores, inds, classes, maps, H, W, present = r
+    scores, inds, classes, maps, H, W, present, unc = r
     if any(v is None for v in maps.values()):
         raise NotImplementedError("decode_post_packed needs the full 3D detection head set")
     B = scores.shape[0]
     return ops.decode_post(scores, inds, classes, maps, H, W, outputSize,
-                           calibs.reshape(B, 3, 4).float().contiguous(), trans_inv, norm2d, want_det)
+                           calibs.reshape(B, 3, 4).float().contiguous(), trans_inv, norm2d, want_det, uncertainty=unc)
 
 
 def unpack_detections(det, present=None):

@@ -16,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .decode import decode_post_packed
 from .checkpoint import loadModel
 from .model import getModel
@@ -163,15 +163,49 @@ class Detector(object):
             radar_pc = [radar_pc] if radar_pc is not None else None
         return imgInput, img_info, radar_pc
 
-    def _finish(self, outputs, post, metas, img_infos, merge):
+    # ------------------------------------------------------------------------------- depth maps
+    def _depth_maps_device(self, outputs):
+        """-> (keys, (len(keys),B,H,W) uint8 device tensor): one launch (cf_depth_maps), nothing copied yet."""
+        if len(outputs) != 1:
+            raise NotImplementedError("the DLA-34 model yields one output layer; multi-layer depth maps are not on the path")
+        out = outputs[0]
+        keys = ["depth"] + [k for k in ("pc_hm_out", "pc_hm_in", "pc_hm_mid") if k in out]
+        maps = [out["depthMap"] if "depthMap" in out else out["depth2"] if "depth2" in out else out["depth"]]
+        maps += [out[k] for k in keys[1:]]
+        outH, outW = self.config.MODEL.OUTPUT_SIZE
+        for k, t in zip(keys, maps):
+            if t.dim() != 4 or t.shape[1] != 1 or tuple(t.shape[2:]) != (outH, outW):
+                raise ValueError(f"depth_maps: {k} has shape {tuple(t.shape)}, expected (B, 1, {outH}, {outW}) - the "
+                                 "reference's interpolate to MODEL.OUTPUT_SIZE is the identity on this path")
+        return keys, ops.depth_maps(maps)
+
+    def depth_maps(self, outputs):
+        """The `depthmaps` of the reference's `Detector.post_process` (detector.py:351-393): {"depth" (from `depthMap`, else
+        `depth2`, else `depth`), "pc_hm_out", "pc_hm_in" when the model has them} -> (B,H,W) uint8 HOST arrays, each image
+        scaled to its own min .. max.  Min / max, normalisation and the cast run on the device in one launch; only the
+        uint8 maps (a quarter of one fp32 map's bytes each) cross PCIe.  Row 0 and column 0 of image 0 - only image 0 -
+        count as 0, as in the reference; an image whose map is flat (no radar return: an all-zero `pc_hm_in`) is 0 / 0
+        there and all zeros here."""
+        with torch.cuda.device(self.device):
+            keys, dm = self._depth_maps_device(outputs)
+        return self._fetch_depth_maps(keys, dm)
+
+    @staticmethod
+    def _fetch_depth_maps(keys, dm):
+        host = dm.cpu().numpy()
+        return {k: host[i] for i, k in enumerate(keys)}
+
+    def _finish(self, outputs, post, metas, img_infos, merge, dm=None):
         ret = {"outputs": outputs, "post": post, "metas": metas, "img_infos": img_infos}
+        if dm is not None:
+            ret["depthmaps"] = self._fetch_depth_maps(*dm)
         if merge:
             detects = {k: v.cpu() for k, v in unpack_post(post).items()}
             ret["detects"] = detects
             ret["predictBoxes"] = self.merge_outputs(detects)
         return ret
 
-    def run_pipelined(self, batches, merge=True):
+    def run_pipelined(self, batches, merge=True, depthmaps=False):
         """Generator over `batches` of (imgInput, img_info, radar_pc) - the arguments of `run` - yielding, in order and
         bit for bit, what `run` returns for each.  Software pipeline of depth two:
           * batch i+1's frames cross PCIe and are warped / ingested / pillar-expanded (`pre_process`) on a FEED stream
@@ -179,6 +213,8 @@ class Detector(object):
             1600x900 frame, 1.4 ms per 16 frames) leaves the critical path;
           * the results of batch i-1 are fetched (`.cpu()`, `merge_outputs`) after batch i's launches are queued, so the
             device never waits for the host.
+        `depthmaps=True`: as in `run`; the launch is queued behind batch i's decode and the uint8 maps are fetched with the
+        detections of that batch, one batch later.
         The reference gets the same overlap from its DataLoader workers + pinned memory (trainer.py, dataset/); frames
         should sit in pinned host memory for the copy to be asynchronous.  An extension: not in the reference's API."""
         from .streams import _side_streams
@@ -215,30 +251,34 @@ class Detector(object):
                     if t is not None:
                         t.record_stream(main)                       # allocated on the feed stream, consumed on `main`
                 outputs, post = self.process(images, calibs, pc_dep, metas[0])       # batch i: queued on `main`
+                dm = self._depth_maps_device(outputs) if depthmaps else None
                 batch = next(it, None)
                 staged = stage(batch, feed_stream(main)) if batch is not None else None   # batch i+1: beside it
-                done, pending = pending, (outputs, post, metas, infos)
+                done, pending = pending, (outputs, post, metas, infos, merge, dm)
                 if done is not None:
-                    done = self._finish(*done, merge)                                # batch i-1: host side
+                    done = self._finish(*done)                                       # batch i-1: host side
             if done is not None:
                 yield done
         with torch.cuda.device(self.device):
-            last = self._finish(*pending, merge)
+            last = self._finish(*pending)
         yield last
 
-    def run(self, imgInput, img_info=None, radar_pc=None, merge=True, stage_times=False):
+    def run(self, imgInput, img_info=None, radar_pc=None, merge=True, stage_times=False, depthmaps=False):
         """imgInput: (H,W,3) uint8 ndarray, a list of them, or a (B,H,W,3) uint8 tensor; img_info: dict or list of
         dicts (`calib`, and for radar `camera_intrinsic`, `width`, `height`); radar_pc: (R,N) array or list.
         -> {"outputs", "post" (B,K,54) device, "metas", "img_infos" (the batch's own, as a list), "detects" (dict of host
         tensors), "predictBoxes"}.
+
+        `depthmaps=True` adds `ret["depthmaps"]`, the second value of the reference's `post_process` that its `run` hands
+        on (detector.py:107-112, 351-393): see `depth_maps`.  Without it the dict has exactly the keys above.
 
         `stage_times=True` adds the reference's per-stage seconds under the reference's keys (its `@return_time` tracing
         hook, utils/utils.py:52-66 on detector.py:44-470; `ret["load"] ... ret["display"]`, detector.py:140-155) plus
         "tot".  The reference brackets every stage with two device synchronisations; here the device stages are
         bracketed by HIP events on the caller's stream and read back once at the end, so timing a run does not
         serialise host and device: "preprocess" (frame copy + warp + radar ingest + pillars), "net" (forward),
-        "decode" (the fused decode + postProcess launch), "postprocess" 0.0 (inside "decode"), "merge" (host: fetch +
-        box lists), "load" / "display" 0.0 (no file loading, no visualisation on this path)."""
+        "decode" (the fused decode + postProcess launch), "postprocess" 0.0 (inside "decode"; with `depthmaps` the depth-map
+        launch), "merge" (host: fetch + box lists), "load" / "display" 0.0 (no file loading, no visualisation on this path)."""
         imgInput, img_info, radar_pc = self._as_batch(imgInput, img_info, radar_pc)
         marks, mark = [], None
         with torch.cuda.device(self.device):
@@ -259,11 +299,14 @@ class Detector(object):
             outputs, post = self.process(images, calibs, pc_dep, metas[0], mark)
             if stage_times:
                 mark("decode")
+            dm = self._depth_maps_device(outputs) if depthmaps else None
+            if stage_times and depthmaps:
+                mark("postprocess")
         if not stage_times:
-            return self._finish(outputs, post, metas, img_info, merge)
+            return self._finish(outputs, post, metas, img_info, merge, dm)
         marks[-1][1].synchronize()
         t_merge = time.perf_counter()
-        ret = self._finish(outputs, post, metas, img_info, merge)
+        ret = self._finish(outputs, post, metas, img_info, merge, dm)
         t_end = time.perf_counter()
         ret.update({"load": 0.0, "postprocess": 0.0, "display": 0.0, "merge": t_end - t_merge, "tot": t_end - t_host})
         for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):

@@ -598,18 +598,37 @@ def _decode_args(scores, inds, classes, maps: dict, H, W, out_hw, norm2d, det):
     return a, keep
 
 
-def decode_gather(scores, inds, classes, maps: dict, H, W, out_hw, norm2d=False):
-    """maps: optional NCHW tensors under reg/wh/depth/rot/dim/amodal/att/vel -> det (B,K,33)."""
+def _uncertainty_map(uncertainty, B, H, W):
+    """The `uncertainty` head's map as the contiguous fp32 (B,1,H,W) buffer cf_decode_*_unc read (None stays None)."""
+    if uncertainty is None:
+        return None
+    _need_cuda(uncertainty)
+    if uncertainty.dtype != torch.float32 or tuple(uncertainty.shape) != (B, 1, H, W):
+        raise _lib.CfHipError(f"uncertainty must be a float32 ({B},1,{H},{W}) map, got {uncertainty.dtype} "
+                              f"{tuple(uncertainty.shape)}")
+    return uncertainty if uncertainty.is_contiguous() else uncertainty.contiguous()
+
+
+def decode_gather(scores, inds, classes, maps: dict, H, W, out_hw, norm2d=False, uncertainty=None):
+    """maps: optional NCHW tensors under reg/wh/depth/rot/dim/amodal/att/vel -> det (B,K,33).
+    uncertainty: the (B,1,H,W) map of the `uncertainty` head: column 0 becomes score * exp(-exp(u)) at the peak
+    (cf_decode_gather_unc); `scores` itself is never written."""
     B, K = scores.shape
     det = torch.empty((B, K, 33), device=scores.device, dtype=torch.float32)
     a, _keep = _decode_args(scores, inds, classes, maps, H, W, out_hw, norm2d, det)
-    _lib.check(_lib.load().cf_decode_gather(C.byref(a), _lib.stream_ptr()), "cf_decode_gather")
+    unc = _uncertainty_map(uncertainty, B, H, W)
+    if unc is None:
+        _lib.check(_lib.load().cf_decode_gather(C.byref(a), _lib.stream_ptr()), "cf_decode_gather")
+    else:
+        _lib.check(_lib.load().cf_decode_gather_unc(C.byref(a), unc.data_ptr(), _lib.stream_ptr()), "cf_decode_gather_unc")
     return det
 
 
-def decode_post(scores, inds, classes, maps: dict, H, W, out_hw, calib, trans_inv, norm2d=False, want_det=False):
+def decode_post(scores, inds, classes, maps: dict, H, W, out_hw, calib, trans_inv, norm2d=False, want_det=False,
+                uncertainty=None):
     """cf_decode_post: decode rows and postProcess rows in one launch -> post (B,K,54) [, det (B,K,33)].
-    calib (B,3,4) f32, trans_inv (2,3) f32 device (output map -> source image affine)."""
+    calib (B,3,4) f32, trans_inv (2,3) f32 device (output map -> source image affine).  uncertainty: as in
+    decode_gather (cf_decode_post_unc)."""
     _need_cuda(calib, trans_inv)
     B, K = scores.shape
     dev = scores.device
@@ -620,9 +639,37 @@ def decode_post(scores, inds, classes, maps: dict, H, W, out_hw, calib, trans_in
         raise _lib.CfHipError("cf_decode_post: calib must be contiguous float32 (B,3,4)")
     if trans_inv.dtype != torch.float32 or not trans_inv.is_contiguous() or trans_inv.numel() != 6:
         raise _lib.CfHipError("cf_decode_post: trans_inv must be contiguous float32 (2,3)")
-    _lib.check(_lib.load().cf_decode_post(C.byref(a), calib.data_ptr(), trans_inv.data_ptr(), post.data_ptr(),
-                                          _lib.stream_ptr()), "cf_decode_post")
+    unc = _uncertainty_map(uncertainty, B, H, W)
+    if unc is None:
+        _lib.check(_lib.load().cf_decode_post(C.byref(a), calib.data_ptr(), trans_inv.data_ptr(), post.data_ptr(),
+                                              _lib.stream_ptr()), "cf_decode_post")
+    else:
+        _lib.check(_lib.load().cf_decode_post_unc(C.byref(a), unc.data_ptr(), calib.data_ptr(), trans_inv.data_ptr(),
+                                                  post.data_ptr(), _lib.stream_ptr()), "cf_decode_post_unc")
     return (post, det) if want_det else post
+
+
+def depth_maps(maps, out=None):
+    """cf_depth_maps: the normalised uint8 maps of the reference's Detector.post_process (detector.py:381-393) for a list of
+    (B,1,H,W) fp32 device maps of one batch, in one launch -> (len(maps),B,H,W) uint8 device tensor.  Row 0 and column 0 of
+    image 0 count as 0 (the reference's quirk); a flat image gives 0."""
+    maps = list(maps)
+    if not 1 <= len(maps) <= _lib.CF_DEPTH_MAPS_MAX:
+        raise _lib.CfHipError(f"depth_maps: 1..{_lib.CF_DEPTH_MAPS_MAX} maps, got {len(maps)}")
+    _need_cuda(*maps)
+    B, one, H, W = maps[0].shape
+    for t in maps:
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, 1, H, W):
+            raise _lib.CfHipError(f"depth_maps: every map must be float32 ({B},1,{H},{W}), got {t.dtype} {tuple(t.shape)}")
+    # a channel view of a wider tensor (pc_hm_in = pc_dep[:, :1]) is read in place: only its batch stride differs
+    keep = [t if (B == 1 or t.stride(0) >= H * W) and t.stride(2) == W and t.stride(3) == 1 else t.contiguous() for t in maps]
+    if out is None:
+        out = torch.empty((len(keep), B, H, W), device=keep[0].device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (len(keep), B, H, W)
+    ptrs = (_lib._f * len(keep))(*(t.data_ptr() for t in keep))
+    strides = (C.c_long * len(keep))(*(max(t.stride(0), H * W) for t in keep))
+    _lib.check(_lib.load().cf_depth_maps(ptrs, strides, len(keep), B, H, W, out.data_ptr(), _lib.stream_ptr()), "cf_depth_maps")
+    return out
 
 
 def serialize_nuscenes(post, trans_matrix, velocity_matrix, cs_rot=None, pose_rot=None, sample_ptr=None,

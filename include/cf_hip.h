@@ -490,6 +490,26 @@ int cf_post_process(const float* det, const float* calib, const float* trans_inv
 int cf_decode_post(const cf_decode_args* a, const float* calib, const float* trans_inv, float* post,
                    void* stream);
 
+/* cf_decode_gather_unc / cf_decode_post_unc: cf_decode_gather / cf_decode_post for a model with the `uncertainty`
+ * head (TRAIN.UNCERTAINTY_LOSS: config/utils.py:100-102).  uncertainty: the head's (B,1,H,W) f32 NCHW map.  The score
+ * written to column 0 of the (B,K,33) and (B,K,54) rows is score * exp(-exp(u)) with u read at the peak pixel
+ * (model/decode.py:80-85; precise expf, fp32).  a->scores is only read and the rows keep the order of the K peaks (the
+ * reference does not sort again either); every other column is what the plain call writes.  The plain calls ARE these
+ * kernels with a NULL map. */
+int cf_decode_gather_unc(const cf_decode_args* a, const float* uncertainty, void* stream);
+int cf_decode_post_unc(const cf_decode_args* a, const float* uncertainty, const float* calib, const float* trans_inv,
+                       float* post, void* stream);
+
+/* cf_depth_maps: the normalised uint8 maps of Detector.post_process (detector.py:381-393; `ret["depthmaps"]` of
+ * Detector.run) for n_maps (<= CF_DEPTH_MAPS_MAX) maps of one batch in ONE launch.  maps: HOST array of n_maps device
+ * pointers, each a (B,1,H,W) f32 map whose images are contiguous H*W planes batch_strides[m] floats apart (HOST array; NULL:
+ * H*W - a channel-0 view of a (B,C,H,W) tensor passes C*H*W); out (n_maps,B,H,W) uint8.  Per image: row 0 and column 0 of image 0 (only) count
+ * as 0, then ((x - min) / (max - min)) * 255 truncated, each operation rounded in fp32 - numpy's bytes.  A flat image
+ * (0 / 0, whose cast numpy leaves undefined) gives 0. */
+#define CF_DEPTH_MAPS_MAX 8
+int cf_depth_maps(const float* const* maps, const long* batch_strides, int n_maps, int B, int H, int W, uint8_t* out,
+                  void* stream);
+
 /* cf_serialize_nuscenes: post-processed detections -> the numeric content of the nuScenes result
  * file, replaces dataset/datasets/nuscenes.py:416-482 (getEvalFormatItem) and the per-sample merge +
  * top-500 of nuscenes.py:536-553 (convert_eval_format); SURVEY §8(f) rank 4.
