@@ -34,6 +34,12 @@ class DcnArgs(C.Structure):
                 ("mx_scale", C.c_float)]
 
 
+class DcnBwdArgs(C.Structure):
+    _fields_ = [("gout", _f), ("weight", _f), ("x", _f), ("offmask", _f), ("B", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("C", C.c_int32), ("N", C.c_int32), ("gx", _f), ("gom", _f), ("gw", _f), ("gbias", _f),
+                ("workspace", _f), ("workspace_bytes", C.c_size_t)]
+
+
 CF_MAX_HEADS = 12
 CF_DEPTH_MAPS_MAX = 8
 
@@ -120,6 +126,9 @@ SYMBOLS = {
     "cf_dcn_v2_fused": (_i, [C.POINTER(DcnArgs), _f]),
     "cf_dcn_v2_f16x3": (_i, [C.POINTER(DcnArgs), _f]),
     "cf_dcn_v2_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "cf_dcn_v2_bwd_data": (_i, [C.POINTER(DcnBwdArgs), _f]),
+    "cf_dcn_v2_bwd_weight": (_i, [C.POINTER(DcnBwdArgs), _f]),
+    "cf_dcn_v2_bwd_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
     "cf_upsample_dw": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _f]),
     "cf_maxpool2x2": (_i, [_f, _f, _i, _i, _i, _i, _f]),
     "cf_nchw_to_nhwc4": (_i, [_f, _f, _i, _i, _i, _i, _f]),

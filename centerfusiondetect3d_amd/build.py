@@ -23,6 +23,7 @@ COMMON = os.environ.get("CF_EXTRA_FLAGS", "").split() + ["-O3", "-std=c++17", "-
 SOURCES = [
     ("cf_gemm.hip", []),
     ("cf_gemm_f16.hip", []),
+    ("cf_dcn_bwd.hip", []),
     ("cf_conv3x3_f16.hip", []),
     ("cf_stem.hip", []),
     ("cf_stem_early.hip", []),

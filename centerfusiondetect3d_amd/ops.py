@@ -393,6 +393,101 @@ def _pair(v):
     return (int(v), int(v)) if isinstance(v, int) else tuple(int(e) for e in v)
 
 
+def _deform_conv2d_forward(input, offset, weight, bias, mask):
+    """The forward launches of `deform_conv2d` (arguments already checked) -> (out NCHW, x NHWC, offmask NHWC)."""
+    B, Cin, H, W = input.shape
+    dev = input.device
+    pd = _packed_dcn(weight, bias)
+    x = nchw_to_nhwc(input.float().contiguous())
+    om = torch.empty((B, H, W, 32), device=dev, dtype=torch.float32)
+    nchw_to_nhwc(offset.float().contiguous(), om, 0)
+    if mask is None:
+        om[..., 18:27] = 1.0
+    else:
+        nchw_to_nhwc(mask.float().contiguous(), om, 18)
+    out = torch.empty((B, H, W, pd.n_pad), device=dev, dtype=torch.float32)     # (any Cout: the row stride is N_pad)
+    nbytes = _lib.load().cf_dcn_v2_workspace_bytes(B, H, W, pd.c, pd.n_pad)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    in_scale = None
+    if _DCN_RANGE_CHECK and not torch.cuda.is_current_stream_capturing():
+        in_scale = in_scale_for(float(absmax(x).item()))          # (raises on NaN / inf)
+    a = dcn_args(pd, x, om, 32, B, H, W, out, pd.n_pad, ACT_NONE, precise=True, workspace=ws, in_scale=in_scale)
+    a.mask_activated = 1
+    run_dcn(a)
+    return nhwc_to_nchw(out, channels=pd.n), x, om
+
+
+def dcn_bwd_args(gout, x, offmask, weight=None, gx=None, gom=None, gw=None, gbias=None, workspace=None) -> _lib.DcnBwdArgs:
+    """The argument block of cf_dcn_v2_bwd_data / cf_dcn_v2_bwd_weight: gout (B,H,W,N), x (B,H,W,C), offmask (B,H,W,32 - the
+    mask ACTIVATED), all fp32 NHWC; weight: the raw (N,C,3,3); gx must arrive zeroed."""
+    _need_cuda(gout, x, offmask, weight, gx, gom, gw, gbias, workspace)
+    for t in (gout, x, offmask, weight, gx, gom, gw, gbias):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.CfHipError("dcn backward: contiguous float32 tensors only")
+    a = _lib.DcnBwdArgs()
+    a.B, a.H, a.W, a.C = x.shape
+    a.N = gout.shape[-1]
+    if tuple(gout.shape[:3]) != tuple(x.shape[:3]) or tuple(offmask.shape) != tuple(x.shape[:3]) + (32,):
+        raise _lib.CfHipError("dcn backward: gout / x / offmask disagree in shape")
+    a.gout, a.x, a.offmask, a.weight = gout.data_ptr(), x.data_ptr(), offmask.data_ptr(), _lib.ptr(weight)
+    a.gx, a.gom, a.gw, a.gbias = _lib.ptr(gx), _lib.ptr(gom), _lib.ptr(gw), _lib.ptr(gbias)
+    if workspace is not None:
+        a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    return a
+
+
+def run_dcn_bwd_data(a: _lib.DcnBwdArgs):
+    """gx (float atomics) and gom of the deformable convolution (cf_dcn_v2_bwd_data)."""
+    _lib.check(_lib.load().cf_dcn_v2_bwd_data(C.byref(a), _lib.stream_ptr()), "cf_dcn_v2_bwd_data")
+
+
+def run_dcn_bwd_weight(a: _lib.DcnBwdArgs):
+    """gw and gbias of the deformable convolution, slab-reduced in a fixed order (cf_dcn_v2_bwd_weight)."""
+    _lib.check(_lib.load().cf_dcn_v2_bwd_weight(C.byref(a), _lib.stream_ptr()), "cf_dcn_v2_bwd_weight")
+
+
+class _DeformConv2dFn(torch.autograd.Function):
+    """`deform_conv2d` under autograd: the forward's launches, the NHWC input / offset-mask buffers they built and the raw
+    weight saved; backward on cf_dcn_v2_bwd_data / cf_dcn_v2_bwd_weight, only what `needs_input_grad` asks for."""
+
+    @staticmethod
+    def forward(ctx, input, offset, weight, bias, mask):
+        out, x, om = _deform_conv2d_forward(input, offset, weight, bias, mask)
+        w = weight.detach()
+        ctx.save_for_backward(x, om, w if w.dtype == torch.float32 and w.is_contiguous() else w.float().contiguous())
+        ctx.dtypes = tuple(None if t is None else t.dtype for t in (input, offset, weight, bias, mask))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        x, om, w = ctx.saved_tensors
+        need_x, need_off, need_w, need_b, need_m = ctx.needs_input_grad
+        B, H, W, Cin = x.shape
+        dev = x.device
+        gout = nchw_to_nhwc(grad_output.float().contiguous())
+        gx = gom = gw = gb = None
+        if need_x or need_off or need_m:
+            gx = torch.zeros((B, H, W, Cin), device=dev, dtype=torch.float32) if need_x else None
+            gom = torch.empty((B, H, W, 32), device=dev, dtype=torch.float32) if (need_off or need_m) else None
+            run_dcn_bwd_data(dcn_bwd_args(gout, x, om, weight=w, gx=gx, gom=gom))
+        if need_w or need_b:
+            gw = torch.empty_like(w) if need_w else None
+            gb = torch.empty(w.shape[0], device=dev, dtype=torch.float32) if need_b else None
+            nbytes = _lib.load().cf_dcn_v2_bwd_workspace_bytes(B, H, W, Cin, w.shape[0])
+            ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            run_dcn_bwd_weight(dcn_bwd_args(gout, x, om, gw=gw, gbias=gb, workspace=ws))
+
+        def om_channels(first, n):            # channels first .. first + n of gom as an NCHW map
+            res = torch.empty((B, n, H, W), device=dev, dtype=torch.float32)
+            _lib.check(_lib.load().cf_nhwc_to_nchw(gom.data_ptr() + 4 * first, res.data_ptr(), B, H, W, n, 32,
+                                                   _lib.stream_ptr()), "cf_nhwc_to_nchw")
+            return res
+        cast = lambda g, i: g if g is None or ctx.dtypes[i] == torch.float32 else g.to(ctx.dtypes[i])
+        return (cast(nhwc_to_nchw(gx) if need_x else None, 0), cast(om_channels(0, 18) if need_off else None, 1),
+                cast(gw, 2), cast(gb, 3), cast(om_channels(18, 9) if need_m else None, 4))
+
+
 def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), mask=None):
     """Operator-level drop-in for `torchvision.ops.deform_conv2d` as the reference calls it
     (model/networks/dla.py:461-470) - same signature, same semantics: `input` (B,Cin,H,W),
@@ -405,7 +500,19 @@ def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0
     cf_dcn_v2_f16x3 with `mask_activated`, cf_nhwc_to_nchw.  The module path (DLASeg) never takes this route: there
     the maps stay NHWC and the mask logits go in raw.  Only the configuration the reference uses is implemented -
     3x3, stride 1, padding 1, dilation 1, one group, one offset group, Cin a multiple of 32; anything else raises
-    NotImplementedError (no fallback)."""
+    NotImplementedError (no fallback).
+
+    Autograd: the operator is differentiable in all five tensor arguments (input, offset, weight, bias, mask), once
+    (no double backward), fp32 only (no autocast).  With grad mode on and at least one of them requiring grad the same
+    launches run inside a `torch.autograd.Function` that keeps the NHWC input and offset-mask buffers and the raw weight;
+    backward runs cf_dcn_v2_bwd_data (input, offset, mask) and cf_dcn_v2_bwd_weight (weight, bias), each only when
+    `needs_input_grad` asks for one of its outputs, on the exact fp32-input MFMA.  The input gradient is summed with float
+    atomics and can differ in the last bits from run to run; the weight and bias gradients are slab sums added in a
+    fixed order and cannot.  At an integer sampling position the offset gradient is the right-hand derivative, as
+    torchvision's is.  The range check and the packed-weight cache behave as in inference: an optimizer's in-place step
+    bumps the weight's version, so the next forward packs it again.  Otherwise (no_grad, nothing requiring grad) the
+    inference path runs as it always did and the result carries no grad_fn.  The module path (`DLASeg`) stays
+    eval-only."""
     _need_cuda(input, offset, weight, bias, mask)
     if input.dim() != 4 or weight.dim() != 4:
         raise ValueError("deform_conv2d: input must be (B,Cin,H,W) and weight (Cout,Cin,kh,kw)")
@@ -426,25 +533,9 @@ def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0
         raise ValueError(f"deform_conv2d: mask must be {(B, 9, H, W)}, got {tuple(mask.shape)}")
     if bias is not None and tuple(bias.shape) != (Cout,):
         raise ValueError(f"deform_conv2d: bias must be ({Cout},), got {tuple(bias.shape)}")
-    dev = input.device
-    pd = _packed_dcn(weight, bias)
-    x = nchw_to_nhwc(input.float().contiguous())
-    om = torch.empty((B, H, W, 32), device=dev, dtype=torch.float32)
-    nchw_to_nhwc(offset.float().contiguous(), om, 0)
-    if mask is None:
-        om[..., 18:27] = 1.0
-    else:
-        nchw_to_nhwc(mask.float().contiguous(), om, 18)
-    out = torch.empty((B, H, W, pd.n_pad), device=dev, dtype=torch.float32)     # (any Cout: the row stride is N_pad)
-    nbytes = _lib.load().cf_dcn_v2_workspace_bytes(B, H, W, pd.c, pd.n_pad)
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
-    in_scale = None
-    if _DCN_RANGE_CHECK and not torch.cuda.is_current_stream_capturing():
-        in_scale = in_scale_for(float(absmax(x).item()))          # (raises on NaN / inf)
-    a = dcn_args(pd, x, om, 32, B, H, W, out, pd.n_pad, ACT_NONE, precise=True, workspace=ws, in_scale=in_scale)
-    a.mask_activated = 1
-    run_dcn(a)
-    return nhwc_to_nchw(out, channels=pd.n)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, offset, weight, bias, mask)):
+        return _DeformConv2dFn.apply(input, offset, weight, bias, mask)
+    return _deform_conv2d_forward(input, offset, weight, bias, mask)[0]
 
 
 def upsample_dw(x, weight_kkc, f, skip=None, out=None):

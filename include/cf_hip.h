@@ -335,6 +335,35 @@ int cf_dcn_v2_fused(const cf_dcn_args* a, void* stream);
 int cf_dcn_v2_f16x3(const cf_dcn_args* a, void* stream);
 size_t cf_dcn_v2_workspace_bytes(int B, int H, int W, int C, int N_pad);
 
+/* Backward of the deformable convolution, for autograd behind the operator-level drop-in (ops.deform_conv2d; added
+ * within ABI 7: nothing existing changed).  Replaces the backward torchvision.ops.deform_conv2d registers with autograd
+ * (model/networks/dla.py:461-470 under training).  Everything is fp32 NHWC in the forward's layouts and the forward's one
+ * configuration (3x3, stride 1, pad 1, dil 1, one group, one offset group, C a multiple of 32, any N <= 1024); the
+ * sampling rule is the forward's, floor held constant (at an integer position the offset gradient is the right-hand
+ * derivative).  Products on the exact fp32-input MFMA: no range to guard, nothing clamped. */
+typedef struct cf_dcn_bwd_args {
+  const float* gout;    /* NHWC [B][H][W][N]: gradient of the output                                         */
+  const float* weight;  /* RAW weight [N][C][3][3] (cf_dcn_v2_bwd_data only)                                  */
+  const float* x;       /* NHWC [B][H][W][C]                                                                  */
+  const float* offmask; /* NHWC [B][H][W][32]: dy / dx of tap k in 2k / 2k+1, the ACTIVATED mask in 18..26    */
+  int32_t B, H, W, C, N;
+  float* gx;            /* cf_dcn_v2_bwd_data: NHWC [B][H][W][C], ZEROED by the caller (float atomics add into it:
+                           the last bits can differ from run to run); may be NULL                              */
+  float* gom;           /* cf_dcn_v2_bwd_data: NHWC [B][H][W][32] in offmask's channel order (the mask gradient is
+                           with respect to the activated mask), channels 27..31 zero; plain stores; may be NULL */
+  float* gw;            /* cf_dcn_v2_bwd_weight: [N][C][3][3]; may be NULL                                     */
+  float* gbias;         /* cf_dcn_v2_bwd_weight: [N], the sum of gout over the pixels; may be NULL             */
+  void* workspace;      /* cf_dcn_v2_bwd_weight: cf_dcn_v2_bwd_workspace_bytes(...) bytes - the pixel dimension is
+                           split into slabs whose partial sums a second launch adds in slab order, so gw and gbias
+                           are bitwise reproducible (no float atomics)                                         */
+  size_t workspace_bytes;
+} cf_dcn_bwd_args;
+/* gx and gom; a launch whose two outputs are NULL succeeds and does nothing */
+int cf_dcn_v2_bwd_data(const cf_dcn_bwd_args* a, void* stream);
+/* gw and gbias; a launch whose two outputs are NULL succeeds and does nothing */
+int cf_dcn_v2_bwd_weight(const cf_dcn_bwd_args* a, void* stream);
+size_t cf_dcn_v2_bwd_workspace_bytes(int B, int H, int W, int C, int N);
+
 /* cf_upsample_dw: depthwise transposed conv (k = 2f, stride f, pad f/2, groups = C, no bias),
  * optionally fused with the IDA skip add:  out = convT(x) [+ skip].
  * replaces aten::conv_transpose2d + add of model/networks/dla.py:502-511, 518-524.

@@ -16,7 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "centerfusiondetect3d_amd", "csrc")
 SOURCES = {"cf_conv3x3_f16.hip": ("conv3x3_f16x3_kernel",), "cf_heads.hip": ("head_patch16_kernel",),
            "cf_gemm_f16.hip": ("dcn_f16x3_kernel", "conv_f16x3_kernel"), "cf_post.hip": ("pc_hm_direct_kernel",),
-           "cf_stem_early.hip": ("stem_early_kernel",)}
+           "cf_stem_early.hip": ("stem_early_kernel",),
+           "cf_dcn_bwd.hip": ("dcn_bwd_data_kernel", "dcn_bwd_weight_kernel")}
 
 
 def functions(asm):
@@ -54,7 +55,7 @@ EPILOGUE_KERNELS = ("conv_f16x3_kernel", "dcn_f16x3_kernel", "conv3x3_f16x3_kern
 # kernels whose MFMA loop must be free of scratch traffic (every instantiation the default path launches)
 # kernels of the default path: NO instantiation may use scratch at all (ScratchSize 0 in the compiler's resource summary)
 NO_SCRATCH = ("head_patch16_kernel", "dcn_f16x3_kernel", "conv3x3_f16x3_kernel", "conv_f16x3_kernel",
-              "pc_hm_direct_kernel", "stem_early_kernel")
+              "pc_hm_direct_kernel", "stem_early_kernel", "dcn_bwd_data_kernel", "dcn_bwd_weight_kernel", "dcn_bwd_reduce_kernel")
 
 
 def scratch_sizes(asm):
