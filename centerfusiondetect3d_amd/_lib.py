@@ -126,6 +126,7 @@ SYMBOLS = {
     "cf_dcn_v2_fused": (_i, [C.POINTER(DcnArgs), _f]),
     "cf_dcn_v2_f16x3": (_i, [C.POINTER(DcnArgs), _f]),
     "cf_dcn_v2_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "cf_gemm_tile_form": (_i, [C.c_long, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cf_dcn_v2_bwd_data": (_i, [C.POINTER(DcnBwdArgs), _f]),
     "cf_dcn_v2_bwd_weight": (_i, [C.POINTER(DcnBwdArgs), _f]),
     "cf_dcn_v2_bwd_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),

@@ -456,10 +456,6 @@ __global__ __launch_bounds__(256) void dcn_igemm_kernel(DcnK p) {
   epilogue<TM, TN>(p.ep, m0 + wm * TM * 32, n0 + wn * TN * 32, lane, acc);
 }
 
-struct TileCfg {
-  int bm, bn;
-};
-
 // Launch with `dyn` bytes of dynamic LDS on top of the kernel's static tiles (raises the kernel's
 // dynamic-LDS limit once per instantiation; 160 KiB per workgroup are available on gfx950).
 template <typename K, typename A>
@@ -469,15 +465,31 @@ void launch_dyn(K kernel, int blocks, size_t dyn, hipStream_t st, const A& args)
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), dyn, st, args);
 }
 
-// Tile choice: widest N tile that divides N_pad; 128-row tiles only when the grid still gives every
-// CU (256) at least two workgroups; and when even 64-row tiles leave some CUs with one workgroup
-// while their neighbours hold two (small-M layers: level5, 14x25 / 28x50 neck nodes), halve the N tile.
-TileCfg pick_tile(long M, int N_pad) {
-  TileCfg t;
+enum { CF_FORM_TILE = 0, CF_FORM_N16 = 1 };
+
+struct TileForm {
+  int kind, bm, bn;
+};
+
+// The one place the launch form is chosen (cf_gemm_tile_form reports it, both launchers run it).
+// 16-channel kernel: convolutions with N <= 16 into NHWC, any act it implements.  Otherwise the widest N tile that
+// divides N_pad; 128-row tiles only when the grid still gives every CU (256) at least two workgroups; when even 64-row
+// tiles leave some CUs with one workgroup while their neighbours hold two (small-M layers: level5, 14x25 / 28x50 neck
+// nodes), halve the N tile.  PRECISE doubles the accumulator registers (64-row tiles keep three workgroups per CU) and
+// the DCN's pipelined gather holds 4 corner rows per staged pixel row in registers: both take 64 rows on the wide tiles.
+TileForm pick_form(long M, int N, int N_pad, int out_layout, int act, bool precise, bool dcn) {
+  TileForm t;
+  if (!dcn && N <= 16 && out_layout == CF_LAYOUT_NHWC && act != CF_ACT_SIGMOID_CLAMP) {
+    t.kind = CF_FORM_N16; t.bm = 128; t.bn = 16;
+    return t;
+  }
+  t.kind = CF_FORM_TILE;
   t.bn = (N_pad % 128 == 0) ? 128 : (N_pad % 64 == 0) ? 64 : 32;
   const long blocks128 = ((M + 127) / 128) * (N_pad / t.bn);
   t.bm = blocks128 >= 512 ? 128 : 64;
   if (t.bm == 64 && t.bn == 128 && ((M + 63) / 64) * (N_pad / 128) < 512) t.bn = 64;
+  if ((precise || dcn) && t.bn >= 64) t.bm = 64;
+  if (t.bm == 64 && t.bn == 32) t.bm = 128;  // no 64x32 instantiation: 128x32 (4 x 1 waves) runs it
   return t;
 }
 
@@ -491,17 +503,24 @@ TileCfg pick_tile(long M, int N_pad) {
     else launch_dyn((KERNEL<BM_, BN_, WM_, WN_, false>), MT * NT, dyn_lds, st, ARGS);           \
   } while (0)
 
-#define DISPATCH_TILE(KERNEL, ARGS, FORCE_BM64)                            \
+#define DISPATCH_TILE(KERNEL, ARGS, FORM)                                  \
   do {                                                                     \
-    TileCfg t = pick_tile(M, N_pad);                                       \
-    if ((FORCE_BM64) && t.bn >= 64) t.bm = 64;                             \
+    const TileForm t = (FORM);                                             \
     if (t.bm == 128 && t.bn == 128) LAUNCH_TILE(KERNEL, ARGS, 128, 128, 2, 2); \
     else if (t.bm == 128 && t.bn == 64) LAUNCH_TILE(KERNEL, ARGS, 128, 64, 2, 2); \
-    else if (t.bm == 128 && t.bn == 32) LAUNCH_TILE(KERNEL, ARGS, 128, 32, 4, 1); \
     else if (t.bm == 64 && t.bn == 128) LAUNCH_TILE(KERNEL, ARGS, 64, 128, 1, 4); \
     else if (t.bm == 64 && t.bn == 64) LAUNCH_TILE(KERNEL, ARGS, 64, 64, 2, 2);   \
     else LAUNCH_TILE(KERNEL, ARGS, 128, 32, 4, 1);                         \
   } while (0)
+
+extern "C" int cf_gemm_tile_form(long M, int N, int N_pad, int out_layout, int act, int precise, int dcn,
+                                 int32_t* kind, int32_t* bm, int32_t* bn) {
+  CF_REQUIRE(kind && bm && bn, "cf_gemm_tile_form: null output");
+  CF_REQUIRE(M > 0 && N > 0 && N_pad >= N && N_pad % 32 == 0, "cf_gemm_tile_form: M=%ld N=%d N_pad=%d", M, N, N_pad);
+  const TileForm t = pick_form(M, N, N_pad, dcn ? CF_LAYOUT_NHWC : out_layout, act, precise != 0, dcn != 0);
+  *kind = t.kind; *bm = t.bm; *bn = t.bn;
+  return 0;
+}
 
 extern "C" int cf_conv2d_fused(const cf_conv_args* a, void* stream) {
   CF_REQUIRE(a != nullptr, "cf_conv2d_fused: null args");
@@ -533,14 +552,14 @@ extern "C" int cf_conv2d_fused(const cf_conv_args* a, void* stream) {
   const bool precise = a->precise != 0;
   const size_t dyn_lds = (size_t)(a->K_pad / 4) * sizeof(cf_slot);
   hipStream_t st = (hipStream_t)stream;
-  if (a->N <= 16 && a->out_layout == CF_LAYOUT_NHWC && a->act != CF_ACT_SIGMOID_CLAMP) {
+  const TileForm form = pick_form(M, a->N, N_pad, a->out_layout, a->act, precise, false);
+  if (form.kind == CF_FORM_N16) {
     const int blocks = (int)((M + 127) / 128);
     if (precise) launch_dyn(conv_igemm_n16_kernel<true>, blocks, dyn_lds, st, k);
     else launch_dyn(conv_igemm_n16_kernel<false>, blocks, dyn_lds, st, k);
     return cf_check_launch("cf_conv2d_fused");
   }
-  // PRECISE doubles the accumulator registers: 64-row tiles keep three workgroups per CU
-  DISPATCH_TILE(conv_igemm_kernel, k, precise);
+  DISPATCH_TILE(conv_igemm_kernel, k, form);
   return cf_check_launch("cf_conv2d_fused");
 }
 
@@ -566,7 +585,6 @@ extern "C" int cf_dcn_v2_fused(const cf_dcn_args* a, void* stream) {
   const bool precise = a->precise != 0;
   const size_t dyn_lds = 0;
   hipStream_t st = (hipStream_t)stream;
-  // 64-row tiles: the pipelined gather holds 4 corner rows per staged pixel row in registers
-  DISPATCH_TILE(dcn_igemm_kernel, k, true);
+  DISPATCH_TILE(dcn_igemm_kernel, k, pick_form(M, a->N, N_pad, CF_LAYOUT_NHWC, a->act, precise, true));
   return cf_check_launch("cf_dcn_v2_fused");
 }

@@ -335,6 +335,13 @@ int cf_dcn_v2_fused(const cf_dcn_args* a, void* stream);
 int cf_dcn_v2_f16x3(const cf_dcn_args* a, void* stream);
 size_t cf_dcn_v2_workspace_bytes(int B, int H, int W, int C, int N_pad);
 
+/* What cf_conv2d_fused (dcn = 0) / cf_dcn_v2_fused (dcn = 1) launches for M output pixels: *kind 0 = the 32x32x2 tile
+ * kernel, 1 = the 16-channel kernel; *bm x *bn its tile.  Host arithmetic only, nothing is launched.  The launchers
+ * choose through the same function, so a test can prove which template instantiation a shape reaches (added within
+ * ABI 7: nothing existing changed). */
+int cf_gemm_tile_form(long M, int N, int N_pad, int out_layout, int act, int precise, int dcn,
+                      int32_t* kind, int32_t* bm, int32_t* bn);
+
 /* Backward of the deformable convolution, for autograd behind the operator-level drop-in (ops.deform_conv2d; added
  * within ABI 7: nothing existing changed).  Replaces the backward torchvision.ops.deform_conv2d registers with autograd
  * (model/networks/dla.py:461-470 under training).  Everything is fp32 NHWC in the forward's layouts and the forward's one

@@ -1,5 +1,6 @@
 """GPU parity, operator level: every C-ABI entry point against the CPU oracle on seeded inputs.
-fp32 GEMM-family kernels: rtol 1e-4 / atol 1e-4 (the north-star budget is 1e-3 end to end);
+fp32 GEMM-family kernels: rtol 1e-4 / atol 1e-4 (the north-star budget is 1e-3 end to end), the exact-fp32 convolution and
+DCN against float64 with gates from fp32 yardsticks measured on the same inputs (tests/exact_fp32_ref.py);
 index-path kernels (top-k, frustum, pillar, decode): bit-exact."""
 import os
 
@@ -12,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import dcn_ref, frustum_ref, decode_ref, pillar_ref
 from tests.golden import cases
+from tests import exact_fp32_ref as E
 
 
 @pytest.fixture(scope="module")
@@ -39,31 +41,38 @@ def close(a, b, rtol=1e-4, atol=1e-4):
 
 
 # ------------------------------------------------------------------------------------------ conv
-@pytest.mark.parametrize("B,Ci,Co,H,W,k,stride,act,res", [
-    (2, 16, 16, 40, 56, 3, 1, 1, False),     # level0-like, N_pad 32
-    (2, 16, 32, 40, 56, 3, 2, 1, False),     # level1 stride 2
-    (1, 64, 64, 28, 50, 3, 1, 1, True),      # BasicBlock conv2 + residual
-    (2, 128, 256, 14, 25, 3, 2, 1, False),   # 128-wide N tile, stride 2
-    (1, 512, 512, 7, 13, 3, 1, 1, True),     # small M, long K
-    (3, 64, 27, 23, 31, 3, 1, 0, False),     # conv_offset_mask (N=27), ragged M
-    (1, 256, 10, 16, 24, 1, 1, 0, False),    # head output 1x1
-])
+def _bn_block(y, bn, r, act):
+    """BatchNorm (inference) + residual + ReLU in y's dtype"""
+    t = lambda v: v.to(y.dtype)
+    y = F.batch_norm(y, t(bn[2]), t(bn[3]), t(bn[0]), t(bn[1]), False, 0.0, 1e-5)
+    if r is not None:
+        y = y + t(r)
+    return F.relu(y) if act else y
+
+
+@pytest.mark.parametrize("B,Ci,Co,H,W,k,stride,act,res", E.OPS_CONV_SHAPES)
 def test_conv2d_fused(dev, B, Ci, Co, H, W, k, stride, act, res):
+    """Against float64 (BatchNorm unfolded in the reference), gated by twice the larger of the two fp32 yardsticks of
+    tests/exact_fp32_ref.py on these inputs: torch's fp32 conv + BN, and the precise kernel's blocked summation on the
+    folded weights.  A precise gate may not come out above 1.5e-6."""
     from centerfusiondetect3d_amd import ops, packing
     x, w, b = rnd(B, Ci, H, W, seed=1), rnd(Co, Ci, k, k, seed=2, scale=(Ci * k * k) ** -0.5), rnd(Co, seed=3)
     bn = (torch.rand(Co) + 0.5, rnd(Co, seed=4, scale=0.1), rnd(Co, seed=5, scale=0.1), torch.rand(Co) + 0.5)
-    ref = F.conv2d(x, w, b, stride, k // 2)
-    ref = F.batch_norm(ref, bn[2], bn[3], bn[0], bn[1], False, 0.0, 1e-5)
-    r = rnd(*ref.shape, seed=6) if res else None
-    if res:
-        ref = ref + r
-    if act:
-        ref = F.relu(ref)
+    ref32 = F.conv2d(x, w, b, stride, k // 2)
+    r = rnd(*ref32.shape, seed=6) if res else None
+    ref32 = _bn_block(ref32, bn, r, act)
+    ref64 = _bn_block(F.conv2d(x.double(), w.double(), b.double(), stride, k // 2), bn, r, act)
     wf, bf = packing.fold_bn(w, b, bn)
-    pc = packing.pack_conv(wf, bf, [packing.Source(Ci, Ci)], stride=stride).to(dev)
-    out = ops.conv2d_fused(pc, [nhwc(x).to(dev)], B, H, W, act=act,
-                           residual=nhwc(r).to(dev) if res else None)
-    close(nchw(out), ref)
+    pc = packing.pack_conv(wf, bf, [packing.Source(Ci, Ci)], stride=stride)
+    model = nchw(E.summation_model(pc, [nhwc(x)], B, H, W, True, nhwc(r) if res else None, act))
+    gate, e_t, e_m = E.conv_gate(ref64, ref32, model)
+    assert gate <= E.GATE_CEILING_PRECISE, gate                   # a condition on the inputs
+    pc = pc.to(dev)
+    out = torch.full(ref32.shape[:1] + ref32.shape[2:] + (Co,), float("nan"), device=dev)
+    ops.conv2d_fused(pc, [nhwc(x).to(dev)], B, H, W, act=act, residual=nhwc(r).to(dev) if res else None, out=out)
+    err = E.relerr(nchw(out.cpu()), ref64)
+    print(f"[exact fp32] conv {Ci}->{Co} @{H}x{W}: torch fp32 {e_t:.2e} summation model {e_m:.2e} gate {gate:.2e} | kernel {err:.2e}")
+    assert not bool(torch.isnan(out).any()) and err <= gate, (err, gate)
 
 
 def test_conv2d_multi_source_root_and_small_source(dev):
@@ -119,9 +128,10 @@ def test_conv2d_stem_from_nchw_image_and_nchw_outputs(dev):
 
 
 # ------------------------------------------------------------------------------------------- dcn
-@pytest.mark.parametrize("B,Ci,Co,H,W,mag", [(2, 64, 64, 28, 50, 2.0), (1, 128, 64, 14, 25, 8.0),
-                                             (1, 512, 256, 7, 13, 1.0), (2, 256, 128, 9, 11, 30.0)])
+@pytest.mark.parametrize("B,Ci,Co,H,W,mag", E.OPS_DCN_SHAPES)
 def test_dcn_v2_fused(dev, B, Ci, Co, H, W, mag):
+    """Against the float64 oracle (BatchNorm unfolded), gate: 5e-6 of max|ref| while the fp32 oracle's own error on this case
+    stays below 2.5e-6, else twice it (the rule of the deform_conv2d backward tests)."""
     from centerfusiondetect3d_amd import ops, packing
     x = rnd(B, Ci, H, W, seed=1)
     om = rnd(B, 27, H, W, seed=2)
@@ -129,14 +139,22 @@ def test_dcn_v2_fused(dev, B, Ci, Co, H, W, mag):
     w, b = rnd(Co, Ci, 3, 3, seed=3, scale=(Ci * 9) ** -0.5), rnd(Co, seed=4)
     bn = (torch.rand(Co) + 0.5, rnd(Co, seed=5, scale=0.1), rnd(Co, seed=6, scale=0.1), torch.rand(Co) + 0.5)
     o1, o2, m = torch.chunk(om, 3, dim=1)
-    ref = dcn_ref.deform_conv2d(x, torch.cat((o1, o2), 1), w, b, (1, 1), (1, 1), (1, 1), torch.sigmoid(m))
-    ref = F.relu(F.batch_norm(ref, bn[2], bn[3], bn[0], bn[1], False, 0.0, 1e-5))
+
+    def oracle(dt):
+        t = lambda v: v.to(dt)
+        y = dcn_ref.deform_conv2d(t(x), t(torch.cat((o1, o2), 1)), t(w), t(b), (1, 1), (1, 1), (1, 1), torch.sigmoid(t(m)))
+        return _bn_block(y, bn, None, True)
+    ref64 = oracle(torch.float64)
+    e32 = E.relerr(oracle(torch.float32), ref64)
+    gate = E.dcn_gate([e32])
     wf, bf = packing.fold_bn(w, b, bn)
     pd = packing.pack_dcn(wf, bf).to(dev)
     om32 = torch.zeros(B, H, W, 32)
     om32[..., :27] = nhwc(om)
     out = ops.dcn_v2_fused(pd, nhwc(x).to(dev), om32.to(dev))
-    close(nchw(out), ref, 2e-4, 2e-4)
+    err = E.relerr(nchw(out.cpu()), ref64)
+    print(f"[exact fp32] dcn {Ci}->{Co} @{H}x{W}: fp32 oracle {e32:.2e} gate {gate:.1e} | kernel {err:.2e}")
+    assert err <= gate, (err, gate)
 
 
 def test_dcn_known_answers_on_device(dev):
