@@ -6,7 +6,7 @@ for AMD MI355X (gfx950), behind the reference project's model / decode interface
     outputs = model(images, pc_dep=pc_dep, calib=calib)      # [ {head: (B,C,112,200)} ]
     dets = fusionDecode(outputs, outputSize=(112, 200), K=100)
 """
-from .config import CfgNode, centerfusion_early_config, centerfusion_middle_config, centernet_config, update_heads
+from .config import CfgNode, centerfusion_early_config, centerfusion_middle_config, centernet_config, update_heads, update_loss_weights
 from .model import DLASeg, getModel
 from .decode import fusionDecode, decode_packed, decode_post_packed, unpack_detections, DET_FIELDS, DET_WIDTH
 from .pointcloud import getPcFrustumHeatmap, getAffineTransform, process_point_cloud_batch, radar_to_pc_dep
@@ -14,8 +14,9 @@ from .postprocess import postProcess, post_process_packed, unpack_post, POST_FIE
 from .preprocess import preProcessImages
 from .serialize import NuScenesResults, convert_eval_format
 from .detector import Detector
+from .loss import GenericLoss
 
-__all__ = ["Detector", "NuScenesResults", "convert_eval_format", "decode_post_packed", "preProcessImages", "radar_to_pc_dep", "CfgNode", "centerfusion_early_config", "centerfusion_middle_config", "centernet_config", "update_heads", "DLASeg",
+__all__ = ["GenericLoss", "update_loss_weights", "Detector", "NuScenesResults", "convert_eval_format", "decode_post_packed", "preProcessImages", "radar_to_pc_dep", "CfgNode", "centerfusion_early_config", "centerfusion_middle_config", "centernet_config", "update_heads", "DLASeg",
            "getModel", "fusionDecode", "decode_packed", "unpack_detections", "DET_FIELDS",
            "DET_WIDTH", "getPcFrustumHeatmap", "getAffineTransform", "process_point_cloud_batch", "postProcess",
            "post_process_packed", "unpack_post", "POST_FIELDS", "POST_WIDTH"]

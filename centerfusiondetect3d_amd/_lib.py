@@ -108,6 +108,24 @@ class SerializeArgs(C.Structure):
                 ("max_per_sample", C.c_int32), ("order", _f), ("counts", _f)]
 
 
+CF_LOSS_MAX_HEADS = 16
+CF_LOSS_STATS = 4 + 4 * CF_LOSS_MAX_HEADS
+LOSS_L1, LOSS_L1_UNC, LOSS_BINROT, LOSS_BCE = 0, 1, 2, 3
+
+
+class LossHead(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("channels", C.c_int32), ("map", _f), ("target", _f), ("mask", _f), ("rotbin", _f),
+                ("unc", _f), ("weight", C.c_float), ("gmap", _f), ("gunc", _f)]
+
+
+class LossArgs(C.Structure):
+    _fields_ = [("heat", _f), ("heat_gt", _f), ("centers", _f), ("wh", _f), ("mask", _f), ("cls", _f),
+                ("B", C.c_int32), ("C", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("M", C.c_int32),
+                ("n_heads", C.c_int32), ("out_area", C.c_float), ("heat_weight", C.c_float),
+                ("head", LossHead * CF_LOSS_MAX_HEADS), ("losses", _f), ("total", _f), ("layer_mask", _f), ("stats", _f),
+                ("workspace", _f), ("workspace_bytes", C.c_size_t), ("grad_out", _f), ("gheat", _f)]
+
+
 # every symbol include/cf_hip.h declares: (restype, argtypes)
 _i, _d = C.c_int, C.c_double
 SYMBOLS = {
@@ -130,6 +148,9 @@ SYMBOLS = {
     "cf_dcn_v2_bwd_data": (_i, [C.POINTER(DcnBwdArgs), _f]),
     "cf_dcn_v2_bwd_weight": (_i, [C.POINTER(DcnBwdArgs), _f]),
     "cf_dcn_v2_bwd_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "cf_loss_forward": (_i, [C.POINTER(LossArgs), _f]),
+    "cf_loss_backward": (_i, [C.POINTER(LossArgs), _f]),
+    "cf_loss_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "cf_upsample_dw": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _f]),
     "cf_maxpool2x2": (_i, [_f, _f, _i, _i, _i, _i, _f]),
     "cf_nchw_to_nhwc4": (_i, [_f, _f, _i, _i, _i, _i, _f]),

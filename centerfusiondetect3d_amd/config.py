@@ -38,6 +38,8 @@ def _base():
                       NORM_2D=False, FUSION_STRATEGY="middle", FRUSTUM=True, K=100,
                       INPUT_SIZE=(448, 800), OUTPUT_SIZE=(112, 200),
                       DLA=CfgNode(NODE="DeformConv"))
+    c.LOSS_WEIGHTS = CfgNode(HEATMAP=1.0, AMODAL_OFFSET=1.0, DIMENSION_2D=0.1, DEPTH=1.0, DIMENSION_3D=1.0, ROTATION=1.0,
+                             NUSCENES_ATT=1.0, VELOCITY=1.0, BBOX_2D=0.0, BBOX_3D=0.0, LIDAR_DEPTH=0.0, RADAR_DEPTH=0.0)
     c.TRAIN = CfgNode(UNCERTAINTY_LOSS=False)
     c.TEST = CfgNode(BATCH_SIZE=1)
     return c
@@ -62,6 +64,17 @@ def update_heads(config):
             head_conv.update({"velocity": [256, 256, 256], "nuscenes_att": [256, 256, 256]})
     config.heads = CfgNode(heads)
     config.head_conv = CfgNode(head_conv)
+    return config
+
+
+def update_loss_weights(config):
+    """config.weights, the per-head loss weights, from config.LOSS_WEIGHTS as config/utils.py:109-141 derives them."""
+    lw = config.LOSS_WEIGHTS
+    config.weights = CfgNode(heatmap=lw.HEATMAP, widthHeight=lw.DIMENSION_2D, reg=lw.AMODAL_OFFSET, bbox2d=lw.BBOX_2D,
+                             depth=lw.DEPTH, depth2=lw.DEPTH, rotation=lw.ROTATION, rotation2=lw.ROTATION,
+                             dimension=lw.DIMENSION_3D, amodal_offset=lw.AMODAL_OFFSET, bbox3d=lw.BBOX_3D,
+                             lidar_depth=lw.LIDAR_DEPTH, radar_depth=lw.RADAR_DEPTH, nuscenes_att=lw.NUSCENES_ATT,
+                             velocity=lw.VELOCITY)
     return config
 
 

@@ -538,6 +538,166 @@ def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0
     return _deform_conv2d_forward(input, offset, weight, bias, mask)[0]
 
 
+# ---- the criterion (cf_loss_forward / cf_loss_backward) ----
+LOSS_L1, LOSS_L1_UNC, LOSS_BINROT, LOSS_BCE = _lib.LOSS_L1, _lib.LOSS_L1_UNC, _lib.LOSS_BINROT, _lib.LOSS_BCE
+
+
+def _loss_tensor(t, what, dtype, shape):
+    _need_cuda(t)
+    if t.dtype != dtype:
+        raise _lib.CfHipError(f"generic_loss: {what} must be {dtype}, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.CfHipError(f"generic_loss: {what} must be {tuple(shape)}, got {tuple(t.shape)}")
+    return t.detach().contiguous()
+
+
+def _loss_map(t, what, shape):
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise NotImplementedError(f"generic_loss: {what} must be a float32 map (no autocast, no fp16 / bf16 / float64)")
+    return _loss_tensor(t, what, torch.float32, shape)
+
+
+def _loss_forward(spec, tensors):
+    """tensors: [heat, map_0 .. map_{n-1}, unc | None, heat_gt, centers, wh, mask, cls, (target_i, aux_i | None) ...] ->
+    the argument block (outputs allocated, gradients unset) and what keeps its pointers alive"""
+    n = len(spec["kinds"])
+    heat, maps, unc = tensors[0], tensors[1:1 + n], tensors[1 + n]
+    heat_gt, centers, wh, mask, cls = tensors[2 + n:7 + n]
+    rest = tensors[7 + n:]
+    if heat.dim() != 4:
+        raise _lib.CfHipError("generic_loss: heatmap must be (B,C,h,w)")
+    if n > _lib.CF_LOSS_MAX_HEADS:
+        raise _lib.CfHipError(f"generic_loss: at most {_lib.CF_LOSS_MAX_HEADS} heads")
+    B, Cc, h, w = heat.shape
+    if centers.dim() != 3:
+        raise _lib.CfHipError("generic_loss: heatCenters must be (B,M,2)")
+    M = centers.shape[1]
+    keep = [_loss_map(heat, "heatmap", (B, Cc, h, w)), _loss_tensor(heat_gt, "heatmap target", torch.float32, (B, Cc, h, w)),
+            _loss_tensor(centers, "heatCenters", torch.float32, (B, M, 2)), _loss_tensor(wh, "widthHeight", torch.float32, (B, M, 2)),
+            _loss_tensor(mask, "mask", torch.float32, (B, M)), _loss_tensor(cls, "classIds", torch.int64, (B, M))]
+    a = _lib.LossArgs()
+    a.heat, a.heat_gt, a.centers, a.wh, a.mask, a.cls = (t.data_ptr() for t in keep)
+    a.B, a.C, a.h, a.w, a.M, a.n_heads = B, Cc, h, w, M, n
+    a.out_area, a.heat_weight = float(spec["out_area"]), float(spec["heat_weight"])
+    uncc = None if unc is None else _loss_map(unc, "uncertainty", (B, 1, h, w))
+    keep.append(uncc)
+    for i, (kind, weight) in enumerate(zip(spec["kinds"], spec["weights"])):
+        H = a.head[i]
+        if maps[i].dim() != 4:
+            raise _lib.CfHipError(f"generic_loss: head {i} must be (B,C,h,w)")
+        ch = maps[i].shape[1]
+        m = _loss_map(maps[i], f"head {i}", (B, ch, h, w))
+        target, aux = rest[2 * i], rest[2 * i + 1]
+        t = _loss_tensor(target, f"head {i} target", torch.float32, (B, M, 2 if kind == LOSS_BINROT else ch))
+        keep += [m, t]
+        H.kind, H.channels, H.map, H.target, H.weight = kind, ch, m.data_ptr(), t.data_ptr(), float(weight)
+        if kind == LOSS_BINROT:
+            x = _loss_tensor(aux, f"head {i} rotbin", torch.int64, (B, M, 2))
+            H.rotbin = x.data_ptr()
+            keep.append(x)
+        elif kind == LOSS_BCE:
+            x = _loss_tensor(aux, f"head {i} mask", torch.float32, (B, M, ch))
+            H.mask = x.data_ptr()
+            keep.append(x)
+        elif kind == LOSS_L1_UNC:
+            if uncc is None:
+                raise _lib.CfHipError("generic_loss: an L1_UNC head needs the uncertainty map")
+            H.unc = uncc.data_ptr()
+        elif kind != LOSS_L1:
+            raise _lib.CfHipError(f"generic_loss: unknown head kind {kind}")
+    return a, keep
+
+
+def _loss_run_forward(spec, tensors):
+    a, keep = _loss_forward(spec, tensors)
+    dev = tensors[0].device
+    n = a.n_heads
+    vec = torch.empty(n + 3, device=dev, dtype=torch.float32)
+    total = torch.empty((), device=dev, dtype=torch.float32)
+    stats = torch.empty(_lib.CF_LOSS_STATS, device=dev, dtype=torch.float32)
+    lm = torch.empty((a.B, a.M), device=dev, dtype=torch.bool)
+    nbytes = _lib.load().cf_loss_workspace_bytes(a.B, a.C, a.h, a.w)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    a.losses, a.total, a.stats, a.layer_mask = vec.data_ptr(), total.data_ptr(), stats.data_ptr(), lm.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    _lib.check(_lib.load().cf_loss_forward(C.byref(a), _lib.stream_ptr()), "cf_loss_forward")
+    return total, vec, lm, stats
+
+
+class _GenericLossFn(torch.autograd.Function):
+    """`generic_loss` under autograd: cf_loss_forward, the maps, the targets and the `stats` block saved; backward on
+    cf_loss_backward, a gradient for exactly the maps `needs_input_grad` names, scaled by the incoming gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, spec, *tensors):
+        total, vec, lm, stats = _loss_run_forward(spec, tensors)
+        ctx.spec = spec
+        ctx.save_for_backward(stats, *tensors)
+        ctx.mark_non_differentiable(vec, lm)
+        return total, vec, lm
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gtotal, _gvec, _glm):
+        stats, *tensors = ctx.saved_tensors
+        spec = ctx.spec
+        n = len(spec["kinds"])
+        need = ctx.needs_input_grad[1:2 + n + 1]
+        a, keep = _loss_forward(spec, tensors)
+        dev = stats.device
+        go = gtotal.detach().to(torch.float32).contiguous()
+        a.stats, a.grad_out = stats.data_ptr(), go.data_ptr()
+        grads = [None] * len(tensors)
+        if need[0]:
+            grads[0] = torch.empty(tensors[0].shape, device=dev, dtype=torch.float32)
+            a.gheat = grads[0].data_ptr()
+        sparse = [i for i in range(1, n + 2) if need[i] and tensors[i] is not None]
+        if sparse:     # one zero fill for every scattered gradient (each slice starts on a multiple of four floats)
+            sizes = [(tensors[i].numel() + 3) // 4 * 4 for i in sparse]
+            flat = torch.zeros(sum(sizes), device=dev, dtype=torch.float32)
+            at = 0
+            for i, sz in zip(sparse, sizes):
+                grads[i] = flat[at:at + tensors[i].numel()].view(tensors[i].shape)
+                at += sz
+            for i in range(n):
+                if grads[1 + i] is not None:
+                    a.head[i].gmap = grads[1 + i].data_ptr()
+                if grads[1 + n] is not None and spec["kinds"][i] == LOSS_L1_UNC:
+                    a.head[i].gunc = grads[1 + n].data_ptr()
+        _lib.check(_lib.load().cf_loss_backward(C.byref(a), _lib.stream_ptr()), "cf_loss_backward")
+        return (None, *grads)
+
+
+def generic_loss(heat, heat_gt, centers, wh, mask, cls, heads, heat_weight=1.0, out_area=None, uncertainty=None):
+    """The reference's GenericLoss over one output layer on already-collected tensors (cf_loss_forward; semantics:
+    include/cf_hip.h).  `heat` (B,C,h,w): the probabilities; `heat_gt` its target; `centers` (B,M,2) f32 (x, y);
+    `wh` (B,M,2) f32 (its product is the layer mask); `mask` (B,M) f32; `cls` (B,M) i64.  `heads`: a list, in the order
+    their terms enter the total, of (kind, map, target, aux, weight) with kind LOSS_L1 (aux None), LOSS_L1_UNC (aux None;
+    `uncertainty` (B,1,h,w) is the map both depth heads share), LOSS_BINROT (target = rotres, aux = rotbin i64) or
+    LOSS_BCE (aux = the (B,M,C) mask).  `out_area` defaults to h*w.
+
+    -> (total, vec, layer_mask): `total` a 0-d tensor, `vec` = [heat-map term, one value per head, total, 0.0] (never
+    carries a grad_fn), `layer_mask` (B,M) bool.  Two launches, no host sync, bitwise reproducible values; capturable in a
+    HIP graph.  With grad mode on and a map requiring grad, `total` carries a grad_fn (once differentiable); backward is
+    cf_loss_backward: a dense pass for `heat`, float atomic adds into zero-filled maps for the heads, only for the maps
+    that require a gradient.  Device fp32 tensors only: a CPU tensor raises CfHipError, a non-fp32 map NotImplementedError."""
+    kinds, weights = [int(hd[0]) for hd in heads], [float(hd[4]) for hd in heads]
+    maps = [hd[1] for hd in heads]
+    spec = {"kinds": kinds, "weights": weights, "heat_weight": float(heat_weight),
+            "out_area": float(out_area if out_area is not None else heat.shape[-2] * heat.shape[-1])}
+    tensors = [heat, *maps, uncertainty, heat_gt, centers, wh, mask, cls]
+    for hd in heads:
+        tensors += [hd[2], hd[3]]
+    for t in [heat, *maps, uncertainty]:
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
+            raise NotImplementedError("generic_loss: float32 maps only (no autocast, no fp16 / bf16 / float64)")
+    _need_cuda(*[t for t in tensors if torch.is_tensor(t)])
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [heat, *maps, uncertainty]):
+        return _GenericLossFn.apply(spec, *tensors)
+    with torch.no_grad():
+        return _loss_run_forward(spec, tensors)[:3]
+
+
 def upsample_dw(x, weight_kkc, f, skip=None, out=None):
     _need_cuda(x, weight_kkc, skip)
     B, H, W, Cc = x.shape

@@ -576,6 +576,76 @@ typedef struct cf_serialize_args {
 int cf_serialize_nuscenes(const cf_serialize_args* a, void* stream);
 int cf_serialize_max_candidates(void);
 
+/* The criterion: GenericLoss of model/genericLoss.py over one output layer, forward and backward, with no host sync
+ * (added within ABI 7: nothing existing changed).  replaces: the ~1,300 aten calls and ~20 device-to-host branches of
+ * genericLoss.py:60-302 + losses.py (FastFocalLoss, RegWeightedL1Loss, BinRotLoss, WeightedBCELoss,
+ * UncertaintyDepthLoss) behind modelWithLoss.py:43-55.  Every map is fp32 NCHW, read in place (no NHWC copy).
+ *
+ * Per object row r = b*M + m:  layer mask lm = (wh[r][0] * wh[r][1]) / out_area > 0; where lm is false every per-object
+ * field counts as 0 (pixel 0, mask 0, class 0, targets 0, rotbin 0, attribute mask 0).  Pixel = int(cy) * w + int(cx) from
+ * `centers`, CLAMPED into [0, h*w) (the reference raises on a centre outside the map).
+ *
+ * Head kinds (value = what goes into `losses`; the total adds weight * value unless stated):
+ *   CF_LOSS_L1      sum_c |pred*m - target*m| / (channels * sum m)            (divisor 1e7 when sum m == 0)
+ *   CF_LOSS_L1_UNC  one channel; u = clamp(unc, -10, 10) at the pixel; value = mean of |d| over the rows with m != 0; the
+ *                   TOTAL takes mean of (|d| e^-u + u) over those rows instead (over all B*M rows when none has m != 0)
+ *   CF_LOSS_BINROT  eight channels; two 2-way cross-entropies averaged over the rows with m != 0, plus smooth-L1 on
+ *                   (sin, cos) of rotres averaged over the rows with rotbin[k] != 0 whatever their m; 0 when sum m == 0
+ *   CF_LOSS_BCE     sum mask * bce_with_logits(pred, target) / sum mask        (divisor 1e7 when sum mask == 0)
+ * The heat-map term is FastFocalLoss: -(pos + neg) / sum m, or -neg when sum m == 0. */
+#define CF_LOSS_MAX_HEADS 16
+#define CF_LOSS_L1 0
+#define CF_LOSS_L1_UNC 1
+#define CF_LOSS_BINROT 2
+#define CF_LOSS_BCE 3
+#define CF_LOSS_STATS (4 + 4 * CF_LOSS_MAX_HEADS) /* floats in cf_loss_args.stats */
+
+typedef struct cf_loss_head {
+  int32_t kind;          /* CF_LOSS_*                                                                          */
+  int32_t channels;      /* L1_UNC: 1, BINROT: 8                                                               */
+  const float* map;      /* [B][channels][h][w]                                                                */
+  const float* target;   /* [B][M][channels]; BINROT: rotres [B][M][2]                                         */
+  const float* mask;     /* BCE: [B][M][channels]; the other kinds use cf_loss_args.mask                       */
+  const int64_t* rotbin; /* BINROT: [B][M][2]                                                                  */
+  const float* unc;      /* L1_UNC: the uncertainty map [B][1][h][w]                                           */
+  float weight;          /* of this term in the total                                                          */
+  float* gmap;           /* backward: gradient of `map`, ZEROED by the caller (float atomics add into it), or NULL */
+  float* gunc;           /* backward, L1_UNC: gradient of `unc`, zeroed by the caller (heads may share it), or NULL */
+} cf_loss_head;
+
+typedef struct cf_loss_args {
+  const float* heat;     /* [B][C][h][w] probabilities (after the clamped sigmoid)                             */
+  const float* heat_gt;  /* [B][C][h][w]                                                                       */
+  const float* centers;  /* [B][M][2] (x, y) on the output map                                                 */
+  const float* wh;       /* [B][M][2]: the layer mask comes from its product                                   */
+  const float* mask;     /* [B][M]                                                                             */
+  const int64_t* cls;    /* [B][M], clamped into [0, C)                                                        */
+  int32_t B, C, h, w, M;
+  int32_t n_heads;       /* <= CF_LOSS_MAX_HEADS                                                               */
+  float out_area;        /* MODEL.OUTPUT_SIZE[0] * MODEL.OUTPUT_SIZE[1]                                        */
+  float heat_weight;
+  cf_loss_head head[CF_LOSS_MAX_HEADS];
+  float* losses;         /* forward out [n_heads + 3]: heat-map term, head 0 .. n_heads-1, total, 0.0          */
+  float* total;          /* forward out: the total once more, in a buffer of its own; may be NULL             */
+  uint8_t* layer_mask;   /* forward out [B][M]: lm as 0 / 1; may be NULL                                       */
+  float* stats;          /* [CF_LOSS_STATS]: counts and normalisers, written by forward, read by backward      */
+  void* workspace;       /* forward: cf_loss_workspace_bytes(...) bytes (the per-workgroup partial sums)       */
+  size_t workspace_bytes;
+  const float* grad_out; /* backward: ONE float on the device, the gradient arriving at the total              */
+  float* gheat;          /* backward: gradient of `heat`, every element written (no zeroing needed), or NULL   */
+} cf_loss_args;
+/* Two launches: a grid-stride pass over heat / heat_gt (16-byte loads when both are 16-byte aligned) that leaves one
+ * partial sum per workgroup in `workspace`, then one workgroup over the B*M objects that gathers every head's prediction,
+ * adds the partials in a fixed order, resolves the zero-count branches on the device and writes losses / total / stats.
+ * No float atomics, no memset: the values are bitwise reproducible from call to call. */
+int cf_loss_forward(const cf_loss_args* a, void* stream);
+/* Up to two launches: a dense pass that writes gheat from heat, heat_gt and stats, then a pass over the objects that
+ * adds the positive focal terms into gheat and scatters each head's gradient into gmap / gunc with float atomic adds
+ * (<= B*M*(sum channels + 1) adds; a pixel hit by three or more objects may differ in its last bits from run to run).
+ * Everything is scaled by *grad_out.  Outputs that are NULL are skipped; with all of them NULL nothing is launched. */
+int cf_loss_backward(const cf_loss_args* a, void* stream);
+size_t cf_loss_workspace_bytes(int B, int C, int h, int w);
+
 /* Weight packing runs once per load_state_dict (BatchNorm fold, slot tables, split hi / lo planes, MFMA fragment order).
  * For the f16x3 convolution and DCN operators it is part of this ABI (cf_pack_conv_f16x3, cf_pack_dcn_f16 above: host-side C,
  * byte-identical to the Python packers); the heads', the stem's and the upsample's weights are packed by

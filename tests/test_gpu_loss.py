@@ -1,0 +1,265 @@
+"""GPU: `centerfusiondetect3d_amd.GenericLoss` (cf_loss_forward / cf_loss_backward) against the plain-torch restatement of
+tests/loss_ref.py run in float64 on the CPU at test time (tests/test_loss_cpu.py pins that restatement to the reference's own
+float64 run at 1e-10).
+
+Criterion.  Each loss value: |got - ref| / |ref|.  Each gradient: max|got - ref| / max|ref|.  A value the reference has as 0
+is exactly 0.0; a sparse head's gradient is exactly 0.0 wherever the reference's is (in particular at every pixel no object
+indexes).  Every measured deviation is printed before it is asserted.
+
+The gate.  The project's rule (tests/test_gpu_deform_conv2d_backward.py): 5e-6 where the fp32 reference itself stays under
+2.5e-6 of float64 on every case, otherwise twice its worst error - the kernel's summation order is one more fp32 order and
+nothing else.  The reference's own fp32 run against its float64 run (`e_ref` of tests/golden/loss_cases.npz, worst over the
+values / over the gradients of a case):
+
+    case               values     gradients
+    dense              1.0e-07    8.1e-08
+    tiny               7.0e-08    1.0e-07
+    sparse             1.1e-07    1.3e-07
+    fullmap            7.3e-08    1.4e-07
+    dense_mask0        5.7e-08    1.3e-07
+    dense_unc_train    9.8e-08    1.2e-07
+    dense_unc_eval     1.5e-07    1.1e-07
+    dense_unc_mask0    6.1e-08    1.2e-07
+    dense_camera       1.4e-07    2.3e-07
+    dense_early        1.1e-07    9.7e-08
+    worst              1.5e-07    2.3e-07
+
+Every one is below 2.5e-6, so the gate is 5e-6 for every value and every gradient."""
+import functools
+import math
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from centerfusiondetect3d_amd.loss import GenericLoss  # noqa: F401  (no criterion, no test in this file)
+from tests import loss_ref
+
+GATE = 5e-6
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+@functools.lru_cache(maxsize=None)
+def reference(i):
+    """float64 values and gradients of case i on the CPU: computed once, shared, never written to"""
+    outputs, batch, training = loss_ref.clone_case(i, requires_grad=True, dtype=torch.float64)
+    total, losses = loss_ref.generic_loss(outputs, batch, loss_ref.config_for(i), training, torch.float64)
+    total.backward()
+    return ({k: float(v.detach()) for k, v in losses.items()},
+            {k: (None if v.grad is None else v.grad.detach()) for k, v in outputs[0].items()})
+
+
+def criterion(i):
+    from centerfusiondetect3d_amd import GenericLoss
+    cfg = loss_ref.config_for(i)
+    return GenericLoss(cfg, cfg.DATASET.NUM_CLASSES).train(loss_ref.CASES[i][4])
+
+
+def check_values(tag, losses, ref):
+    assert list(losses) == list(ref)
+    for k, r in ref.items():
+        v = losses[k]
+        assert v.dim() == 0 and v.dtype == torch.float32 and v.grad_fn is None and not v.requires_grad
+        got = float(v)
+        err = abs(got - r) / abs(r) if r != 0 else abs(got)
+        print(f"[loss] {tag}: {k:14s} {got:.8g}  ref {r:.10g}  rel {err:.2e}")
+        if r == 0:
+            assert got == 0.0, (tag, k, got)
+        assert err <= GATE, (tag, k, got, r, err)
+
+
+def check_grad(tag, k, got, ref, scale=1.0):
+    assert got.shape == ref.shape and got.dtype == torch.float32
+    got = got.double().cpu()
+    den = float(ref.abs().max()) * scale
+    err = float((got - ref * scale).abs().max()) / den if den > 0 else float(got.abs().max())
+    print(f"[loss] {tag}: grad {k:14s} max|ref| {den:.4g}  err {err:.2e}")
+    if k != "heatmap":
+        assert bool((got[ref == 0] == 0).all()), (tag, k, "non-zero where the reference is exactly zero")
+    assert err <= GATE, (tag, k, err)
+
+
+@pytest.mark.parametrize("i", range(len(loss_ref.CASES)))
+def test_every_case_against_the_float64_restatement(dev, i):
+    name = loss_ref.NAMES[i]
+    ref_v, ref_g = reference(i)
+    outputs, batch, _ = loss_ref.clone_case(i, device=dev, requires_grad=True)
+    total, losses = criterion(i)(outputs, batch)
+    assert total.dim() == 0 and total.grad_fn is not None
+    assert float(total.detach()) == float(losses["total"])
+    check_values(name, losses, ref_v)
+    total.backward()
+    _, cpu_batch, _ = loss_ref.make_case(i)
+    wh = cpu_batch["widthHeight"]
+    lm = (wh[..., 0] * wh[..., 1]) > 0
+    assert batch["layerMask"].dtype == torch.bool and torch.equal(batch["layerMask"].cpu(), lm[:, None])
+    h, w = outputs[0]["heatmap"].shape[-2:]
+    c = cpu_batch["target"]["heatCenters"]
+    pix = (c[..., 1].long() * w + c[..., 0].long()) * lm
+    hit = torch.zeros(pix.shape[0], h * w, dtype=torch.bool).scatter_(1, pix, True).reshape(-1, 1, h, w)
+    for k, r in ref_g.items():
+        g = outputs[0][k].grad
+        if r is None:
+            assert g is None, (name, k)
+            continue
+        check_grad(name, k, g, r)
+        if k != "heatmap":
+            assert bool((g.cpu()[~hit.expand_as(g)] == 0).all()), (name, k, "gradient on a pixel no object indexes")
+
+
+def test_known_answer_no_objects(dev):
+    """no objects, gt = 0, p = 0.5: the heat-map term is N * 0.25 * ln 2, and so is the total"""
+    from centerfusiondetect3d_amd import ops
+    B, C, h, w, M = 1, 10, 7, 9, 5
+    z = lambda *s, dt=torch.float32: torch.zeros(*s, device=dev, dtype=dt)
+    total, vec, lm = ops.generic_loss(torch.full((B, C, h, w), 0.5, device=dev), z(B, C, h, w), z(B, M, 2), z(B, M, 2), z(B, M),
+                                      z(B, M, dt=torch.int64), [], heat_weight=1.0)
+    want = B * C * h * w * 0.25 * math.log(2.0)
+    err = abs(float(vec[0]) - want) / want
+    print(f"[loss] no objects: {float(vec[0]):.8g}  want {want:.10g}  rel {err:.2e}")
+    assert err <= GATE and float(total) == float(vec[0]) == float(vec[1]) and float(vec[2]) == 0.0
+    assert vec.shape == (3,) and not bool(lm.any()) and total.grad_fn is None
+
+
+def test_known_answer_one_object_one_l1_head(dev):
+    """one object, one L1 head, pred - target given: the term is sum|d| / C, its gradient sign(d) / C on the object's pixel"""
+    from centerfusiondetect3d_amd import ops
+    B, C, h, w, M, ch = 1, 10, 7, 9, 1, 3
+    d = torch.tensor([0.75, -2.5, 0.125])
+    target = torch.tensor([[[1.0, -3.0, 0.5]]])
+    pred = torch.zeros(B, ch, h, w)
+    pred[0, :, 4, 6] = target[0, 0] + d
+    pred = pred.to(dev).requires_grad_(True)
+    heat = torch.full((B, C, h, w), 0.5, device=dev)
+    total, vec, _ = ops.generic_loss(heat, torch.zeros(B, C, h, w, device=dev), torch.tensor([[[6.4, 4.9]]], device=dev),
+                                     torch.tensor([[[3.0, 2.0]]], device=dev), torch.ones(B, M, device=dev),
+                                     torch.zeros(B, M, device=dev, dtype=torch.int64),
+                                     [(ops.LOSS_L1, pred, target.to(dev), None, 2.0)], heat_weight=0.0)
+    want = float(d.abs().sum()) / ch
+    print(f"[loss] one object: {float(vec[1]):.8g}  want {want:.10g}  total {float(total.detach()):.8g}")
+    assert float(vec[1]) == want and float(total.detach()) == 2.0 * want          # (exact in fp32: the numbers are dyadic)
+    total.backward()
+    g = torch.zeros(B, ch, h, w)
+    g[0, :, 4, 6] = 2.0 * torch.sign(d) / ch
+    assert torch.equal(pred.grad.cpu(), g)
+
+
+@pytest.mark.parametrize("i", [0, 3, 5])
+def test_repeated_calls_are_bit_identical(dev, i):
+    outputs, batch, _ = loss_ref.clone_case(i, device=dev)
+    crit = criterion(i)
+    with torch.no_grad():
+        a = torch.stack(list(crit(outputs, batch)[1].values())).cpu()
+        b = torch.stack(list(crit(outputs, batch)[1].values())).cpu()
+    assert torch.equal(a, b)
+
+
+def test_upstream_gradient_scales_the_gradients(dev):
+    i = 5
+    _, ref_g = reference(i)
+    outputs, batch, _ = loss_ref.clone_case(i, device=dev, requires_grad=True)
+    total, _ = criterion(i)(outputs, batch)
+    (3 * total).backward()
+    for k, r in ref_g.items():
+        if r is not None:
+            check_grad("3 * total", k, outputs[0][k].grad, r, scale=3.0)
+
+
+def test_only_the_maps_that_require_grad_get_one(dev):
+    i = 5
+    _, ref_g = reference(i)
+    outputs, batch, _ = loss_ref.clone_case(i, device=dev)
+    outputs[0]["heatmap"].requires_grad_(True)
+    total, _ = criterion(i)(outputs, batch)
+    total.backward()
+    check_grad("heatmap only", "heatmap", outputs[0]["heatmap"].grad, ref_g["heatmap"])
+    assert all(v.grad is None for k, v in outputs[0].items() if k != "heatmap")
+    # the other way round: two sparse heads and the shared uncertainty map, no dense pass
+    outputs, batch, _ = loss_ref.clone_case(i, device=dev)
+    for k in ("rotation2", "depth", "uncertainty"):
+        outputs[0][k].requires_grad_(True)
+    total, _ = criterion(i)(outputs, batch)
+    total.backward()
+    for k, v in outputs[0].items():
+        if k in ("rotation2", "depth", "uncertainty"):
+            check_grad("sparse only", k, v.grad, ref_g[k])
+        else:
+            assert v.grad is None, k
+
+
+def test_no_grad_carries_no_grad_fn(dev):
+    outputs, batch, _ = loss_ref.clone_case(0, device=dev, requires_grad=True)
+    with torch.no_grad():
+        total, losses = criterion(0)(outputs, batch)
+    assert total.grad_fn is None and not total.requires_grad
+    assert all(v.grad_fn is None and not v.requires_grad for v in losses.values())
+    outputs, batch, _ = loss_ref.clone_case(0, device=dev)           # grad mode on, nothing requires grad
+    total, _ = criterion(0)(outputs, batch)
+    assert total.grad_fn is None and not total.requires_grad
+
+
+def _copy_into(dst, src):
+    for k, v in src.items():
+        if isinstance(v, dict):
+            _copy_into(dst[k], v)
+        else:
+            dst[k].copy_(v)
+
+
+def test_forward_is_captured_in_a_graph_and_replayed_on_other_data(dev):
+    """dense -> dense_mask0 (same shapes and heads, every zero-count branch taken on the device): a host sync inside the
+    forward would fail the capture, a branch decided on the host would replay the first case's"""
+    a, b = loss_ref.NAMES.index("dense"), loss_ref.NAMES.index("dense_mask0")
+    outputs, batch, _ = loss_ref.clone_case(a, device=dev)
+    crit = criterion(a)
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream), torch.no_grad():
+        crit(outputs, batch)                                         # warm-up outside the capture
+    torch.cuda.current_stream().wait_stream(stream)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.no_grad(), torch.cuda.graph(graph):
+        total, losses = crit(outputs, batch)
+    graph.replay()
+    torch.cuda.synchronize()
+    check_values("graph, captured case", losses, reference(a)[0])
+    src_out, src_batch, _ = loss_ref.clone_case(b, device=dev)
+    src_batch.pop("layerMask", None)
+    batch.pop("layerMask")
+    _copy_into(outputs[0], src_out[0])
+    _copy_into(batch, src_batch)
+    graph.replay()
+    torch.cuda.synchronize()
+    check_values("graph, replayed on dense_mask0", losses, reference(b)[0])
+    assert float(total) == float(losses["total"])
+
+
+def test_end_to_end_behind_the_model(dev):
+    """DLASeg on the weights and inputs of make_golden_nofrustum.py (B = 2, 32 x 40 maps); its output list goes straight into
+    the criterion; the restatement runs in float64 on the downloaded maps"""
+    from centerfusiondetect3d_amd import GenericLoss, getModel, centerfusion_middle_config, update_loss_weights
+    from tests.golden import cases
+    from tests.golden.make_golden_nofrustum import nofrustum_inputs, H, W
+    cfg = centerfusion_middle_config((H, W))
+    cfg.MODEL.FRUSTUM = False
+    cfg.LOSS_WEIGHTS.update(loss_ref.LOSS_WEIGHTS)
+    update_loss_weights(cfg)
+    m = getModel(cfg)
+    m.load_state_dict(cases.tuned_state_dict(radar=True, seed=0), strict=True)
+    m = m.to(dev).eval()
+    x, pc_dep, calib = nofrustum_inputs()
+    with torch.no_grad():
+        outputs = m(x.to(dev), pc_dep=pc_dep.to(dev), calib=calib.to(dev))
+        cpu_batch = loss_ref.batch_for(outputs)
+        batch = {k: ({kk: vv.to(dev) for kk, vv in v.items()} if isinstance(v, dict) else v.to(dev)) for k, v in cpu_batch.items()}
+        total, losses = GenericLoss(cfg, cfg.DATASET.NUM_CLASSES)(outputs, batch)
+    maps = [{k: v.cpu() for k, v in outputs[0].items() if torch.is_tensor(v)}]
+    _, ref = loss_ref.generic_loss(maps, cpu_batch, cfg, False, torch.float64)
+    check_values("DLASeg -> GenericLoss", losses, {k: float(v) for k, v in ref.items()})
