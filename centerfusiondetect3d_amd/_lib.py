@@ -8,6 +8,7 @@ LIB_PATH = os.path.join(_PKG, "libcfhip.so")
 
 ABI_VERSION = 7      # CF_ABI_VERSION of include/cf_hip.h this binding was written against
 CF_MAX_SRC = 4
+CF_MAX_GROUPS = 4    # layers per grouped launch (cf_conv3x3_f16x3_grouped, cf_dcn_v2_f16x3_grouped)
 ACT_NONE, ACT_RELU, ACT_SIGMOID_CLAMP, ACT_RAW_AND_SIGDEPTH = 0, 1, 2, 3
 LAYOUT_NHWC, LAYOUT_NCHW = 0, 1
 
@@ -134,6 +135,8 @@ SYMBOLS = {
     "cf_conv3x3_f16x3": (_i, [C.POINTER(ConvArgs), _f]),
     "cf_conv3x3_root_f16x3": (_i, [C.POINTER(ConvArgs), C.POINTER(ConvArgs), C.POINTER(C.c_int32), _f]),
     "cf_conv3x3_proj_f16x3": (_i, [C.POINTER(ConvArgs), C.POINTER(C.c_int32), _f]),
+    "cf_conv3x3_f16x3_grouped": (_i, [C.POINTER(C.POINTER(ConvArgs)), C.c_int32, _f]),
+    "cf_conv3x3_grouped_form": (_i, [C.POINTER(C.POINTER(ConvArgs)), C.c_int32, C.POINTER(C.c_int32)]),
     "cf_stem_fused": (_i, [C.POINTER(StemArgs), _f]),
     "cf_stem_fused_early": (_i, [C.POINTER(StemEarlyArgs), _f]),
     "cf_split_bf16": (_i, [_f, _f, C.c_long, _i, _i, _i, _f]),
@@ -144,6 +147,7 @@ SYMBOLS = {
     "cf_dcn_v2_fused": (_i, [C.POINTER(DcnArgs), _f]),
     "cf_dcn_v2_f16x3": (_i, [C.POINTER(DcnArgs), _f]),
     "cf_dcn_v2_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "cf_dcn_v2_f16x3_grouped": (_i, [C.POINTER(C.POINTER(DcnArgs)), C.c_int32, _f]),
     "cf_gemm_tile_form": (_i, [C.c_long, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cf_dcn_v2_bwd_data": (_i, [C.POINTER(DcnBwdArgs), _f]),
     "cf_dcn_v2_bwd_weight": (_i, [C.POINTER(DcnBwdArgs), _f]),

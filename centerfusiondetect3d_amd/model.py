@@ -214,6 +214,9 @@ class DLASeg(nn.Module):
         self.stem_fused = True   # with conv_f16: base_layer + level0 + level1 in one launch (cf_stem.hip)
         self.stem_pool = True    # ... which also writes the level-2 Tree's max-pool of its output (one launch less per trunk)
         self.conv_patch = True   # 3x3 stride-1 f16x3 convs: LDS patch reuse (cf_conv3x3_f16.hip)
+        self.neck_groups = True  # neck without lanes: the same-shape DeformConv projections of an IDA level (dla_up.ida_1.proj_1-2; dla_up.ida_2.
+                                 # proj_1-3 + ida_up.proj_1) as ONE offset-convolution launch and ONE DCN launch per set (plan.py:
+                                 # _Plan._dcn_group); same bits; set before the first forward
         self.root_fuse = True    # one-level Trees: tree2.conv2 + Root as one step (cf_conv3x3_root_f16x3) ...
         self.root_fuse_children = False   # ... also where the Root has further sources (level3.tree2, level4.tree2): same bits, and
                                           # in the two-stream step the two launches are 0.024 ms faster (round 5, 6 of 6 A/B pairs)

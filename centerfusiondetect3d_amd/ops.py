@@ -109,6 +109,51 @@ def conv2d_f16x3(pc: PackedConv, srcs, B, H, W, act=ACT_NONE, residual=None, out
     return out
 
 
+def group_ptrs(blocks):
+    """The host array of argument-block pointers a grouped entry point takes (keep `blocks` alive beside it)."""
+    return (C.POINTER(type(blocks[0])) * len(blocks))(*[C.pointer(b) for b in blocks])
+
+
+def conv3x3_f16x3_grouped(pcs: Sequence[PackedConv], xs, act=ACT_NONE, out=None):
+    """The offset convolutions (N_pad = 32) of up to four same-shape layers on their own inputs as ONE launch
+    (cf_conv3x3_f16x3_grouped).  xs: (B,H,W,C) tensors; -> (G,B,H,W,S), S = `out`'s row stride (default 32: the offmask rows
+    the DCN reads); group g's rows carry the bits of the ungrouped call on (pcs[g], xs[g])."""
+    _need_cuda(*xs, out)
+    B, H, W, _ = xs[0].shape
+    if out is None:
+        out = torch.empty((len(xs), B, H, W, pcs[0].n_pad), device=xs[0].device, dtype=torch.float32)
+    S = out.shape[-1]
+    blocks = [conv_args(pc, [x], [x.shape[-1]], B, H, W, out[g], S, act, None, 0, LAYOUT_NHWC, None, 0, False)
+              for g, (pc, x) in enumerate(zip(pcs, xs))]
+    _lib.check(_lib.load().cf_conv3x3_f16x3_grouped(group_ptrs(blocks), len(blocks), _lib.stream_ptr()), "cf_conv3x3_f16x3_grouped")
+    return out
+
+
+def conv3x3_grouped_form(blocks):
+    """{WC, WP, WK, NU, T2, CT}: the conv3x3_f16x3_kernel_grouped instantiation cf_conv3x3_f16x3_grouped launches for these
+    argument blocks (the launcher's own choice; nothing is launched)."""
+    form = (C.c_int32 * 6)()
+    _lib.check(_lib.load().cf_conv3x3_grouped_form(group_ptrs(blocks), len(blocks), form), "cf_conv3x3_grouped_form")
+    return dict(zip(("WC", "WP", "WK", "NU", "T2", "CT"), form))
+
+
+def dcn_v2_f16x3_grouped(pds: Sequence[PackedDcn], xs, offmask, act=ACT_RELU, k_split=True):
+    """The deformable convolutions of up to four same-shape layers as ONE launch (+ one reduction on K-split maps;
+    cf_dcn_v2_f16x3_grouped).  xs: (B,H,W,C) tensors (two groups may share one); offmask (G,B,H,W,S>=27); -> (G,B,H,W,N)."""
+    _need_cuda(*xs, offmask)
+    B, H, W, _ = xs[0].shape
+    G, pd = len(xs), pds[0]
+    out = torch.empty((G, B, H, W, pd.n), device=xs[0].device, dtype=torch.float32)
+    ws = None
+    if k_split:
+        nbytes = _lib.load().cf_dcn_v2_workspace_bytes(B, H, W, pd.c, pd.n_pad)
+        ws = torch.empty(G * nbytes, device=xs[0].device, dtype=torch.uint8) if nbytes else None
+    blocks = [dcn_args(p_, x, offmask[g], offmask.shape[-1], B, H, W, out[g], pd.n, act, False, workspace=ws)
+              for g, (p_, x) in enumerate(zip(pds, xs))]
+    _lib.check(_lib.load().cf_dcn_v2_f16x3_grouped(group_ptrs(blocks), G, _lib.stream_ptr()), "cf_dcn_v2_f16x3_grouped")
+    return out
+
+
 def conv3x3_proj_f16x3(pc: PackedConv, t, pooled, act=ACT_RELU, out=None):
     """BasicBlock conv2 + the Tree's `project` of the pooled level input in ONE launch (cf_conv3x3_proj_f16x3; pc from
     packing.pack_conv_f16(proj=...)): out = act(conv3x3(t) + project(pooled) + biases)."""

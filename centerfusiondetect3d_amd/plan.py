@@ -63,6 +63,7 @@ class _Plan:
         # the three-hidden-layer heads on the image features (their own launch); their split-bf16 operand where the primary group reads mx rows
         self.early, self.direct_step, self.chained, self.feat_bf = bool(model.isEarly), None, [], None
         self._pooled = {}
+        self._pre = {}           # projection name -> output computed ahead by a grouped launch (_ida / _dcn_group)
         # heads: per-call output tensors are patched into the arg blocks in `outs` / `tails`; the other steps patched per
         # call; the radar maps the secondary heads read; the frustum chain's top-k; the decoder's peaks lane
         self.primary, self.radar, self.frustum, self.K = [], False, False, int(model.config.MODEL.K)
@@ -213,13 +214,69 @@ class _Plan:
         self._add(p, 2.0 * B * h * w * pd.n * 9 * pd.c, (fn, C.byref(a)), a)
         return o
 
-    def _ida(self, p, layers, startp, endp, final_out=None, feat=False):
+    def _dcn_group(self, members):
+        """The DeformConv projections `members` = [(layer name, input)] - one shape, independent inputs - as TWO launches:
+        cf_conv3x3_f16x3_grouped (the offset convolutions) and cf_dcn_v2_f16x3_grouped (+ its one reduction on K-split maps).
+        `om` and the outputs are slices of one buffer each; every layer keeps its own weights, bias and pre-scale, so each
+        slice carries the bits of that layer's own two launches.  -> the output slices, in order.
+        The step names stay per layer (tools/layer_times.py, time_launch): the set's launch sits under its FIRST member
+        with the FLOPs of all of them; the other members' names point at the same step and carry no FLOPs."""
+        m, B, G = self._m, self.B, len(members)
+        _, h, w, c = members[0][1].shape
+        pd0 = self._pk[members[0][0]]
+        om = self._buf(G, B, h, w, 32)
+        out = self._buf(G, B, h, w, pd0.n)
+        nbytes = self.lib.cf_dcn_v2_workspace_bytes(B, h, w, pd0.c, pd0.n_pad)
+        ws = self._buf(G * nbytes, dtype=torch.uint8) if nbytes else None
+        ca, da, flops_c, flops_d = [], [], 0.0, 0.0
+        for g, (name, x) in enumerate(members):
+            pc, pd = self._pk[name + ".conv_offset_mask"], self._pk[name]
+            ca.append(ops.conv_args(pc, [x], [c], B, h, w, om[g], 32, ACT_NONE, None, 0, LAYOUT_NHWC, None, 0, m.precise,
+                                    in_scale=m._scale(name + ".conv_offset_mask")))
+            da.append(ops.dcn_args(pd, x, om[g], 32, B, h, w, out[g], pd.n, ACT_RELU, precise=m.precise, workspace=ws,
+                                   in_scale=m._scale(name)))
+            self.inputs[name + ".conv_offset_mask"], self.inputs[name] = [x], [x]
+            flops_c += 2.0 * B * h * w * pc.n * 9 * sum(int(v) for v in pc.real_cin)
+            flops_d += 2.0 * B * h * w * pd.n * 9 * pd.c
+        cp, dp = ops.group_ptrs(ca), ops.group_ptrs(da)
+        # (the other members first: whoever inverts step_index - all_launch_times - then finds the first member's name last)
+        for name, _ in members[1:]:
+            self.step_index[name + ".conv_offset_mask"], self.step_index[name] = len(self.steps), len(self.steps) + 1
+            self.step_flops[name + ".conv_offset_mask"] = self.step_flops[name] = 0.0
+        first = members[0][0]
+        self._add(first + ".conv_offset_mask", flops_c, (self.lib.cf_conv3x3_f16x3_grouped, cp, G), cp, ca)
+        self._add(first, flops_d, (self.lib.cf_dcn_v2_f16x3_grouped, dp, G), dp, da)
+        return [out[g] for g in range(G)]
+
+    def _groupable(self, name, x):
+        """(shape key) of a projection the grouped launches can carry - split-fp16 offset convolution on the patch kernel
+        (N_pad = 32) and split-fp16 DCN with whole-row epilogue - or None."""
+        m, pc, pd = self._m, self._pk[name + ".conv_offset_mask"], self._pk[name]
+        ok = pc.out_scale > 0 and getattr(pc, "patch", False) and m.conv_patch and pc.n_pad == 32 and \
+            pd.out_scale > 0 and pd.n % 4 == 0 and pd.n_pad <= 128
+        return (tuple(x.shape), pc.k_pad, pd.c, pd.n, pd.n_pad) if ok else None
+
+    def _ida(self, p, layers, startp, endp, final_out=None, feat=False, also=()):
         """IDAUp.forward (dla.py:518-524).  The projections of one IDA level read maps that all exist when the level
         starts and do not depend on each other or on the nodes, so with `self.use_lanes` they are issued on a side
         stream (offset conv + DCN per projection) while the caller's stream runs the node chain
         upsample+skip -> offset conv -> DCN, waiting for projection j right before it consumes it.  Small
-        batches only: there a single launch cannot fill the chip and the two chains overlap (bit-identical)."""
+        batches only: there a single launch cannot fill the chip and the two chains overlap (bit-identical).
+        Without lanes (model.neck_groups): the level's projections of ONE shape - and those of a later level in `also` =
+        [(name, input)] whose inputs exist already - run as one grouped pair of launches in front of the node chain
+        (_dcn_group); their outputs wait in `self._pre` for the level that consumes them."""
         projs = {}
+        if self._m.neck_groups and not self.use_lanes:
+            sets = {}
+            for name, x in [(f"{p}.proj_{i - startp}", layers[i]) for i in range(startp + 1, endp)] + list(also):
+                key = self._groupable(name, x) if name not in self._pre else None
+                if key is not None:
+                    sets.setdefault(key, []).append((name, x))
+            for members in sets.values():
+                for k in range(0, len(members), _lib.CF_MAX_GROUPS):
+                    part = members[k:k + _lib.CF_MAX_GROUPS]
+                    if len(part) > 1:
+                        self._pre.update(zip([n for n, _ in part], self._dcn_group(part)))
         if self.use_lanes:
             self.ctl("rec", 0, ev0 := self.new_event())      # everything the projections read is complete here
             self.ctl("wait", 1, ev0)
@@ -234,6 +291,8 @@ class _Plan:
             if self.use_lanes:
                 proj, ev = projs[i]
                 self.ctl("wait", 0, ev)
+            elif f"{p}.proj_{j}" in self._pre:
+                proj = self._pre.pop(f"{p}.proj_{j}")
             else:
                 proj = self._dcn_node(f"{p}.proj_{j}", layers[i])
             wk, f = self._pk[f"{p}.up_{j}"]
@@ -280,8 +339,11 @@ class _Plan:
         self.debug = {f"y{i}": t for i, t in enumerate(layers) if t is not None}
         # ---- DLA-up + IDA-up neck
         out = [layers[-1]]
-        for i in range(len(layers) - 2 - 1):
-            self._ida(f"dla_up.ida_{i}", layers, len(layers) - i - 2, len(layers))
+        n_ida = len(layers) - 2 - 1
+        for i in range(n_ida):
+            # ida_up.proj_1 reads what the level before the last leaves in layers[-1] (out[1] below): it joins the last level's set
+            also = [("ida_up.proj_1", layers[-1])] if i == n_ida - 1 and i > 0 else []
+            self._ida(f"dla_up.ida_{i}", layers, len(layers) - i - 2, len(layers), also=also)
             out.insert(0, layers[-1])
         for i, t in enumerate(out):
             self.debug[f"up{i}"] = t

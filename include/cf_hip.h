@@ -30,6 +30,7 @@ extern "C" {
 #define CF_ELAUNCH (-5)
 
 #define CF_MAX_SRC 4
+#define CF_MAX_GROUPS 4 /* layers per cf_conv3x3_f16x3_grouped / cf_dcn_v2_f16x3_grouped launch */
 
 /* activation / epilogue modes of cf_conv2d_fused and cf_dcn_v2_fused */
 #define CF_ACT_NONE 0
@@ -167,6 +168,19 @@ int cf_conv3x3_root_f16x3(const cf_conv_args* conv, const cf_conv_args* root, co
  * cf_conv2d_f16x3 on the same slot table (the same products in the same order; the same bits wherever the patch tiling
  * does not split K over waves - maps of at most 512 pixels with 256+ channels do, as in cf_conv3x3_f16x3). */
 int cf_conv3x3_proj_f16x3(const cf_conv_args* a, const int32_t* src_channels, void* stream);
+
+/* cf_conv3x3_f16x3_grouped (added within ABI 7: nothing existing changed): n_groups (1 .. CF_MAX_GROUPS) DeformConv.conv_offset_mask
+ * convolutions (dla.py:406-414; N_pad = 32) of ONE geometry on independent inputs as one launch - the projections of an IDA
+ * level (dla.py:518-524) depend neither on each other nor on the node chain.  `groups` (host array) holds one argument block
+ * per layer as for cf_conv3x3_f16x3: src[0], weight, bias, in_scale and out_scale are the layer's own; B, H, W, src_c[0], K_pad,
+ * N, N_pad, out_stride and act must agree; no residual; group g's `out` must be group 0's + g * B*H*W * out_stride floats (one
+ * buffer, rows [g M, (g + 1) M)).  A workgroup serves one group: group g's rows are bit for bit those of cf_conv3x3_f16x3 on
+ * block g.  n_groups = 1 is that call.  Anything else (n_groups outside the range, a null block, another N_pad) -> CF_EINVAL,
+ * nothing is launched. */
+int cf_conv3x3_f16x3_grouped(const cf_conv_args* const* groups, int32_t n_groups, void* stream);
+/* ... and the tiling that launch takes, form[6] = {WC, WP, WK, patch units per thread, tiled patch, 32-pixel column tiles per
+ * wave} (the template arguments of conv3x3_f16x3_kernel_grouped): host arithmetic only, chosen by the launcher's own code. */
+int cf_conv3x3_grouped_form(const cf_conv_args* const* groups, int32_t n_groups, int32_t* form);
 
 /* ---- (ABI 5) host-side weight preparation: SURVEY 8(b) "cf_pack_weights" (one-time BN fold + layout) -------------------------
  * Pure CPU functions (no stream, no device memory): HOST pointers in, HOST buffers out; the caller copies the results to the
@@ -334,6 +348,15 @@ int cf_dcn_v2_fused(const cf_dcn_args* a, void* stream);
  * (packing.pack_dcn_f16), out_scale = 2^-(s+4).  x / offmask / out stay fp32 NHWC. */
 int cf_dcn_v2_f16x3(const cf_dcn_args* a, void* stream);
 size_t cf_dcn_v2_workspace_bytes(int B, int H, int W, int C, int N_pad);
+
+/* cf_dcn_v2_f16x3_grouped (added within ABI 7: nothing existing changed): the deformable convolutions of n_groups
+ * (1 .. CF_MAX_GROUPS) same-shape layers as one launch (and, on K-split maps, ONE reduction over all groups' rows).  `groups`
+ * (host array): one block per layer as for cf_dcn_v2_f16x3; x, weight, bias, in_scale and out_scale are the layer's own (two
+ * groups may read the same x); the geometry, N, N_pad, strides, act and mask_activated must agree; `offmask` and `out` of
+ * group g must be group 0's + g * B*H*W rows; the workspace is group 0's (n_groups x cf_dcn_v2_workspace_bytes(...), or null: no K
+ * split).  out_split_bf16 / out_mx are refused (CF_EINVAL) when n_groups > 1.  Group g's rows equal cf_dcn_v2_f16x3 on block g
+ * (same workspace choice) bit for bit: same descriptors, same K order, same K split, partial sums added in the same order. */
+int cf_dcn_v2_f16x3_grouped(const cf_dcn_args* const* groups, int32_t n_groups, void* stream);
 
 /* What cf_conv2d_fused (dcn = 0) / cf_dcn_v2_fused (dcn = 1) launches for M output pixels: *kind 0 = the 32x32x2 tile
  * kernel, 1 = the 16-channel kernel; *bm x *bn its tile.  Host arithmetic only, nothing is launched.  The launchers
