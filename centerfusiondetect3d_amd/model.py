@@ -430,7 +430,7 @@ class DLASeg(nn.Module):
             self._mx_active = mx
             # the mx rows' pre-scale: one for both head groups (they read the same rows)
             fr = [self._ranges[n] for n in ("heads.primary.0", "heads.secondary.0") if self._ranges and n in self._ranges]
-            self._feat_scale = ops.in_scale_for(max(fr), self.range_headroom) if (mx and fr) else ops.DEFAULT_IN_SCALE
+            self._feat_scale = ops.in_scale_for_large(max(fr), self.range_headroom) if (mx and fr) else ops.DEFAULT_IN_SCALE
             def first(h, srcs, mx=mx):
                 if mx:
                     d = packing.pack_head_first_mx(hw(h, 0), hb(h, 0), pc=len(srcs) == 2, feat_scale=self._feat_scale)

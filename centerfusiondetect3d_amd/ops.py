@@ -24,16 +24,50 @@ DEFAULT_IN_SCALE = 16.0     # activation pre-scale of the f16x3 / mx kernels (cf
 F16_MAX = 65504.0
 
 
-def in_scale_for(absmax, headroom=8.0):
-    """The activation pre-scale (a power of two) for a layer whose inputs reach `absmax`: the default 16 while that leaves a
-    factor 4 to the fp16 limit, otherwise the largest power of two that keeps absmax * scale <= 65504 / headroom."""
+IN_SCALE_KEEP_MIN = 2.0 ** -6   # the default pre-scale is kept down to this max |x| (below, the lo half turns fp16-subnormal)
+IN_SCALE_MAX = 2.0 ** 32        # cap of the lower branch: out_scale = 2^-s / in_scale stays a normal fp32
+F32_MIN_NORMAL = 2.0 ** -126
+
+
+def _largest_pow2_scale(a, limit):
+    """The largest power of two s with a * s <= limit (a, limit > 0)."""
+    import math
+    p = math.floor(math.log2(limit / a))
+    while a * 2.0 ** (p + 1) <= limit:
+        p += 1
+    while a * 2.0 ** p > limit:
+        p -= 1
+    return 2.0 ** p
+
+
+def in_scale_for_large(absmax, headroom=8.0):
+    """The upper branch of `in_scale_for` alone: 16 unless max |x| * 16 comes within a factor 4 of the fp16 limit.  The rule
+    of the heads' mx rows (block floating point: no lower-end problem)."""
     a = float(absmax)
     if not (a == a) or a == float("inf"):
         raise _lib.CfHipError("activation range is not finite (NaN / inf in a layer input)")
     if a * DEFAULT_IN_SCALE <= F16_MAX / 4.0:
         return DEFAULT_IN_SCALE
-    import math
-    return 2.0 ** math.floor(math.log2(F16_MAX / headroom / a))
+    return _largest_pow2_scale(a, F16_MAX / headroom)
+
+
+def in_scale_for(absmax, headroom=8.0):
+    """The activation pre-scale (a power of two) for a layer whose inputs reach `absmax`: the default 16 while
+    2^-6 <= absmax and absmax * 16 leaves a factor 4 to the fp16 limit (and for absmax == 0: an empty map); otherwise the
+    largest power of two that keeps absmax * scale <= 65504 / headroom - below 2^-6 that RAISES the scale (capped at 2^32),
+    so the lo half of the split stays a normal fp16."""
+    a = float(absmax)
+    if a == 0.0 or a >= IN_SCALE_KEEP_MIN or not (a == a):
+        return in_scale_for_large(a, headroom)
+    return min(IN_SCALE_MAX, _largest_pow2_scale(a, F16_MAX / headroom))
+
+
+def _scaled_out_scale(out_scale, in_scale, what):
+    """out_scale of a launch whose activation pre-scale is `in_scale` instead of 16; it must stay a normal fp32."""
+    s = out_scale * DEFAULT_IN_SCALE / float(in_scale)
+    if out_scale > 0 and not (F32_MIN_NORMAL <= s < float("inf")):
+        raise _lib.CfHipError(f"{what}: out_scale {s!r} for in_scale {float(in_scale)!r} is not a normal fp32")
+    return s
 
 
 def conv_args(pc: PackedConv, srcs: Sequence[torch.Tensor], src_strides: Sequence[int], B, H, W,
@@ -61,7 +95,7 @@ def conv_args(pc: PackedConv, srcs: Sequence[torch.Tensor], src_strides: Sequenc
     a.out_scale = float(getattr(pc, "out_scale", 0.0))        # 2^-(s+4): the packer's figure at the default pre-scale
     if in_scale is not None and float(in_scale) != DEFAULT_IN_SCALE:
         a.in_scale = float(in_scale)
-        a.out_scale = a.out_scale * DEFAULT_IN_SCALE / float(in_scale)
+        a.out_scale = _scaled_out_scale(a.out_scale, in_scale, "conv_args")
     return a
 
 
@@ -95,16 +129,16 @@ def run_conv_f16(a: _lib.ConvArgs, patch=False):
         _lib.check(_lib.load().cf_conv2d_f16x3(C.byref(a), _lib.stream_ptr()), "cf_conv2d_f16x3")
 
 
-def conv2d_f16x3(pc: PackedConv, srcs, B, H, W, act=ACT_NONE, residual=None, out=None, patch=None):
+def conv2d_f16x3(pc: PackedConv, srcs, B, H, W, act=ACT_NONE, residual=None, out=None, patch=None, in_scale=None):
     """fp32 NHWC in / out, split-fp16 products (packing.pack_conv_f16).  patch: use the LDS-patch
-    3x3 kernel (default: whenever the packing allows it)."""
+    3x3 kernel (default: whenever the packing allows it).  in_scale: the activation pre-scale (None = 16)."""
     _need_cuda(*srcs, residual)
     Ho = (H + 2 * pc.pad - pc.kh) // pc.stride + 1
     Wo = (W + 2 * pc.pad - pc.kh) // pc.stride + 1
     if out is None:
         out = torch.empty((B, Ho, Wo, pc.n), device=srcs[0].device, dtype=torch.float32)
     a = conv_args(pc, srcs, [s.shape[-1] for s in srcs], B, H, W, out, out.shape[-1], act, residual,
-                  residual.shape[-1] if residual is not None else 0, LAYOUT_NHWC, None, 0, False)
+                  residual.shape[-1] if residual is not None else 0, LAYOUT_NHWC, None, 0, False, in_scale=in_scale)
     run_conv_f16(a, pc.patch if patch is None else patch)
     return out
 
@@ -114,16 +148,18 @@ def group_ptrs(blocks):
     return (C.POINTER(type(blocks[0])) * len(blocks))(*[C.pointer(b) for b in blocks])
 
 
-def conv3x3_f16x3_grouped(pcs: Sequence[PackedConv], xs, act=ACT_NONE, out=None):
+def conv3x3_f16x3_grouped(pcs: Sequence[PackedConv], xs, act=ACT_NONE, out=None, in_scales=None):
     """The offset convolutions (N_pad = 32) of up to four same-shape layers on their own inputs as ONE launch
     (cf_conv3x3_f16x3_grouped).  xs: (B,H,W,C) tensors; -> (G,B,H,W,S), S = `out`'s row stride (default 32: the offmask rows
-    the DCN reads); group g's rows carry the bits of the ungrouped call on (pcs[g], xs[g])."""
+    the DCN reads); group g's rows carry the bits of the ungrouped call on (pcs[g], xs[g]).  in_scales: one activation
+    pre-scale per group (None = 16 each)."""
     _need_cuda(*xs, out)
     B, H, W, _ = xs[0].shape
     if out is None:
         out = torch.empty((len(xs), B, H, W, pcs[0].n_pad), device=xs[0].device, dtype=torch.float32)
     S = out.shape[-1]
-    blocks = [conv_args(pc, [x], [x.shape[-1]], B, H, W, out[g], S, act, None, 0, LAYOUT_NHWC, None, 0, False)
+    blocks = [conv_args(pc, [x], [x.shape[-1]], B, H, W, out[g], S, act, None, 0, LAYOUT_NHWC, None, 0, False,
+                        in_scale=None if in_scales is None else in_scales[g])
               for g, (pc, x) in enumerate(zip(pcs, xs))]
     _lib.check(_lib.load().cf_conv3x3_f16x3_grouped(group_ptrs(blocks), len(blocks), _lib.stream_ptr()), "cf_conv3x3_f16x3_grouped")
     return out
@@ -137,9 +173,10 @@ def conv3x3_grouped_form(blocks):
     return dict(zip(("WC", "WP", "WK", "NU", "T2", "CT"), form))
 
 
-def dcn_v2_f16x3_grouped(pds: Sequence[PackedDcn], xs, offmask, act=ACT_RELU, k_split=True):
+def dcn_v2_f16x3_grouped(pds: Sequence[PackedDcn], xs, offmask, act=ACT_RELU, k_split=True, in_scales=None):
     """The deformable convolutions of up to four same-shape layers as ONE launch (+ one reduction on K-split maps;
-    cf_dcn_v2_f16x3_grouped).  xs: (B,H,W,C) tensors (two groups may share one); offmask (G,B,H,W,S>=27); -> (G,B,H,W,N)."""
+    cf_dcn_v2_f16x3_grouped).  xs: (B,H,W,C) tensors (two groups may share one); offmask (G,B,H,W,S>=27); -> (G,B,H,W,N).
+    in_scales: one activation pre-scale per group (None = 16 each)."""
     _need_cuda(*xs, offmask)
     B, H, W, _ = xs[0].shape
     G, pd = len(xs), pds[0]
@@ -148,38 +185,43 @@ def dcn_v2_f16x3_grouped(pds: Sequence[PackedDcn], xs, offmask, act=ACT_RELU, k_
     if k_split:
         nbytes = _lib.load().cf_dcn_v2_workspace_bytes(B, H, W, pd.c, pd.n_pad)
         ws = torch.empty(G * nbytes, device=xs[0].device, dtype=torch.uint8) if nbytes else None
-    blocks = [dcn_args(p_, x, offmask[g], offmask.shape[-1], B, H, W, out[g], pd.n, act, False, workspace=ws)
+    blocks = [dcn_args(p_, x, offmask[g], offmask.shape[-1], B, H, W, out[g], pd.n, act, False, workspace=ws,
+                       in_scale=None if in_scales is None else in_scales[g])
               for g, (p_, x) in enumerate(zip(pds, xs))]
     _lib.check(_lib.load().cf_dcn_v2_f16x3_grouped(group_ptrs(blocks), G, _lib.stream_ptr()), "cf_dcn_v2_f16x3_grouped")
     return out
 
 
-def conv3x3_proj_f16x3(pc: PackedConv, t, pooled, act=ACT_RELU, out=None):
+def conv3x3_proj_f16x3(pc: PackedConv, t, pooled, act=ACT_RELU, out=None, in_scale=None):
     """BasicBlock conv2 + the Tree's `project` of the pooled level input in ONE launch (cf_conv3x3_proj_f16x3; pc from
-    packing.pack_conv_f16(proj=...)): out = act(conv3x3(t) + project(pooled) + biases)."""
+    packing.pack_conv_f16(proj=...)): out = act(conv3x3(t) + project(pooled) + biases).  in_scale: ONE activation pre-scale
+    for both operands (None = 16)."""
     _need_cuda(t, pooled)
     assert pc.proj_k > 0, "weights packed without a projection"
     B, H, W, _ = t.shape
     if out is None:
         out = torch.empty((B, H, W, pc.n), device=t.device, dtype=torch.float32)
     a = conv_args(pc, [t, pooled], [t.shape[-1], pooled.shape[-1]], B, H, W, out, out.shape[-1], act, None, 0,
-                  LAYOUT_NHWC, None, 0, False)
+                  LAYOUT_NHWC, None, 0, False, in_scale=in_scale)
     ch = (C.c_int32 * 2)(*[int(c) for c in pc.real_cin])
     _lib.check(_lib.load().cf_conv3x3_proj_f16x3(C.byref(a), ch, _lib.stream_ptr()), "cf_conv3x3_proj_f16x3")
     return out
 
 
-def conv3x3_root_f16x3(pc2: PackedConv, pc_root: PackedConv, t, x1, children=(), act_root=ACT_RELU, x2_out=None):
+def conv3x3_root_f16x3(pc2: PackedConv, pc_root: PackedConv, t, x1, children=(), act_root=ACT_RELU, x2_out=None,
+                       in_scale=None, root_in_scale=None):
     """One-level Tree tail: x2 = ReLU(conv3x3(t) + x1), out = act(Root([x2, x1, *children])) as ONE launch where the shape
-    allows (cf_conv3x3_root_f16x3), the two launches otherwise - same bits.  -> (out, x2 buffer: written only on the fallback)."""
+    allows (cf_conv3x3_root_f16x3), the two launches otherwise - same bits.  -> (out, x2 buffer: written only on the fallback).
+    in_scale / root_in_scale: the activation pre-scales of conv2's input and of the Root's operands (None = 16)."""
     _need_cuda(t, x1, *children)
     B, H, W, _ = t.shape
     x2 = torch.empty((B, H, W, pc2.n), device=t.device, dtype=torch.float32) if x2_out is None else x2_out
     out = torch.empty((B, H, W, pc_root.n), device=t.device, dtype=torch.float32)
-    a = conv_args(pc2, [t], [t.shape[-1]], B, H, W, x2, x2.shape[-1], ACT_RELU, x1, x1.shape[-1], LAYOUT_NHWC, None, 0, False)
+    a = conv_args(pc2, [t], [t.shape[-1]], B, H, W, x2, x2.shape[-1], ACT_RELU, x1, x1.shape[-1], LAYOUT_NHWC, None, 0, False,
+                  in_scale=in_scale)
     srcs = [x2, x1, *children]
     r = conv_args(pc_root, srcs, [s.shape[-1] for s in srcs], B, H, W, out, out.shape[-1], act_root, None, 0,
-                  LAYOUT_NHWC, None, 0, False)
+                  LAYOUT_NHWC, None, 0, False, in_scale=root_in_scale)
     ch = (C.c_int32 * len(srcs))(*[int(c) for c in pc_root.real_cin])
     _lib.check(_lib.load().cf_conv3x3_root_f16x3(C.byref(a), C.byref(r), ch, _lib.stream_ptr()), "cf_conv3x3_root_f16x3")
     return out, x2
@@ -293,7 +335,7 @@ def dcn_args(pd: PackedDcn, x, offmask, om_stride, B, H, W, out, out_stride, act
     a.out_scale = float(getattr(pd, "out_scale", 0.0))
     if in_scale is not None and float(in_scale) != DEFAULT_IN_SCALE:
         a.in_scale = float(in_scale)
-        a.out_scale = a.out_scale * DEFAULT_IN_SCALE / float(in_scale)
+        a.out_scale = _scaled_out_scale(a.out_scale, in_scale, "dcn_args")
     if mx_scale is not None and float(mx_scale) != DEFAULT_IN_SCALE:
         a.mx_scale = float(mx_scale)
     if out_split is not None:            # (B,H,W,2,Cs) bf16: split copy for the head kernels (f16x3 kernel only)
@@ -311,8 +353,9 @@ def run_dcn(a: _lib.DcnArgs):
     _lib.check(fn(C.byref(a), _lib.stream_ptr()), "cf_dcn_v2")
 
 
-def dcn_v2_fused(pd: PackedDcn, x, offmask, act=ACT_RELU, precise=True, k_split=True):
-    """x (B,H,W,C) NHWC, offmask (B,H,W,S>=27) NHWC raw conv_offset_mask output."""
+def dcn_v2_fused(pd: PackedDcn, x, offmask, act=ACT_RELU, precise=True, k_split=True, in_scale=None):
+    """x (B,H,W,C) NHWC, offmask (B,H,W,S>=27) NHWC raw conv_offset_mask output.  in_scale (f16x3 packing): the activation
+    pre-scale (None = 16)."""
     _need_cuda(x, offmask)
     B, H, W, _ = x.shape
     out = torch.empty((B, H, W, pd.n), device=x.device, dtype=torch.float32)
@@ -320,7 +363,7 @@ def dcn_v2_fused(pd: PackedDcn, x, offmask, act=ACT_RELU, precise=True, k_split=
     if k_split and getattr(pd, "out_scale", 0.0) > 0:
         nbytes = _lib.load().cf_dcn_v2_workspace_bytes(B, H, W, pd.c, pd.n_pad)
         ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8) if nbytes else None
-    a = dcn_args(pd, x, offmask, offmask.shape[-1], B, H, W, out, pd.n, act, precise, workspace=ws)
+    a = dcn_args(pd, x, offmask, offmask.shape[-1], B, H, W, out, pd.n, act, precise, workspace=ws, in_scale=in_scale)
     run_dcn(a)
     return out
 
@@ -1080,18 +1123,18 @@ def stem_args(ps, x, out, shape=None, out_pool=None, in_scales=None, into=None) 
         for i, (s, name) in enumerate(zip(in_scales, ("scale_base", "scale_level0", "scale_level1"))):
             if s is not None and float(s) != DEFAULT_IN_SCALE:
                 a.in_scale[i] = float(s)
-                setattr(a, name, getattr(a, name) * DEFAULT_IN_SCALE / float(s))
+                setattr(a, name, _scaled_out_scale(getattr(a, name), s, "stem_args"))
     return a
 
 
-def stem_fused(ps, x, out=None, out_pool=None):
+def stem_fused(ps, x, out=None, out_pool=None, in_scales=None):
     """images (B, C<=3, H, W) fp32 NCHW -> level1 map (B, H/2, W/2, 32) fp32 NHWC (packing.pack_stem); out_pool: also its
-    MaxPool2d(2, 2), (B, H/4, W/4, 32)."""
+    MaxPool2d(2, 2), (B, H/4, W/4, 32).  in_scales: as stem_args."""
     _need_cuda(x, out_pool)
     B, Cc, H, W = x.shape
     if out is None:
         out = torch.empty((B, H // 2, W // 2, 32), device=x.device, dtype=torch.float32)
-    a = stem_args(ps, x.contiguous(), out, out_pool=out_pool)
+    a = stem_args(ps, x.contiguous(), out, out_pool=out_pool, in_scales=in_scales)
     _lib.check(_lib.load().cf_stem_fused(C.byref(a), _lib.stream_ptr()), "cf_stem_fused")
     return out
 
@@ -1108,16 +1151,17 @@ def stem_early_args(ps, x, pc, out, shape=None, out_pool=None, in_scales=None) -
     return e
 
 
-def stem_fused_early(ps, x, pc, out=None, out_pool=None):
+def stem_fused_early(ps, x, pc, out=None, out_pool=None, in_scales=None):
     """Early radar fusion: images (B, 3, H, W) + radar map (B, 3, H/4, W/4), both fp32 NCHW -> the level1 map of the six-channel
-    stem, (B, H/2, W/2, 32) fp32 NHWC (packing.pack_stem_early); out_pool as in stem_fused.  The map is read, not written."""
+    stem, (B, H/2, W/2, 32) fp32 NHWC (packing.pack_stem_early); out_pool as in stem_fused.  The map is read, not written.
+    in_scales: as stem_args."""
     _need_cuda(x, pc, out_pool)
     B, Cc, H, W = x.shape
     if pc.dim() != 4 or pc.shape[0] != B or pc.shape[1] != 3 or pc.dtype != torch.float32:
         raise _lib.CfHipError(f"stem_fused_early: the radar map must be float32 (B, 3, H/4, W/4), got {tuple(pc.shape)}")
     if out is None:
         out = torch.empty((B, H // 2, W // 2, 32), device=x.device, dtype=torch.float32)
-    a = stem_early_args(ps, x.contiguous(), pc.contiguous(), out, out_pool=out_pool)
+    a = stem_early_args(ps, x.contiguous(), pc.contiguous(), out, out_pool=out_pool, in_scales=in_scales)
     _lib.check(_lib.load().cf_stem_fused_early(C.byref(a), _lib.stream_ptr()), "cf_stem_fused_early")
     return out
 

@@ -1,7 +1,10 @@
 """GPU parity, operator level: every C-ABI entry point against the CPU oracle on seeded inputs.
 fp32 GEMM-family kernels: rtol 1e-4 / atol 1e-4 (the north-star budget is 1e-3 end to end), the exact-fp32 convolution and
 DCN against float64 with gates from fp32 yardsticks measured on the same inputs (tests/exact_fp32_ref.py);
-index-path kernels (top-k, frustum, pillar, decode): bit-exact."""
+index-path kernels (top-k, frustum, pillar, decode): bit-exact.
+The split-fp16 (f16x3) tests of this file draw inputs of magnitude 1 or more and run at the default activation pre-scale 16
+only: every f16x3 entry point and launch form off that default - a different 2^k per group and operand, inputs of 2^-24 .. 2^10
+against float64 with per-channel gates - is tests/test_gpu_f16x3_range.py's, on rows taken from the tables below."""
 import os
 
 import numpy as np

@@ -93,10 +93,11 @@ def test_conv3x3_in_scale_matches_fp32_oracle(dev, amp):
         ops.run_conv_f16(a, patch=True)
 
 
-@pytest.mark.parametrize("amp", [1.0, 5.0e4])
+@pytest.mark.parametrize("amp", [1.0, 5.0e4, 2.0 ** -12, 2.0 ** -24])
 def test_deform_conv2d_operator_accepts_any_range(dev, amp):
-    """ops.deform_conv2d (= torchvision's signature) measures its input and picks the pre-scale: inputs of 5e4 come out as
-    accurate as inputs of 1; with the check switched off they are clamped (the documented contract of that switch)."""
+    """ops.deform_conv2d (= torchvision's signature) measures its input and picks the pre-scale: inputs of 5e4, 2^-12 and 2^-24
+    come out as accurate as inputs of 1 (the bias is scaled with them, so max|ref| hides nothing); with the check switched
+    off large inputs are clamped (the documented contract of that switch)."""
     from centerfusiondetect3d_amd import ops
     from oracle import dcn_ref
     g = torch.Generator().manual_seed(5)
@@ -105,7 +106,7 @@ def test_deform_conv2d_operator_accepts_any_range(dev, amp):
     off = torch.randn(B, 18, H, W, generator=g) * 1.5
     mask = torch.sigmoid(torch.randn(B, 9, H, W, generator=g))
     w = torch.randn(N, C, 3, 3, generator=g) * 0.05
-    b = torch.randn(N, generator=g)
+    b = torch.randn(N, generator=g) * amp
     ref = dcn_ref.deform_conv2d(x.double(), off.double(), w.double(), b.double(), padding=(1, 1), mask=mask.double())
     got = ops.deform_conv2d(x.to(dev), off.to(dev), w.to(dev), b.to(dev), padding=(1, 1), mask=mask.to(dev))
     err = float((got.double().cpu() - ref).abs().max() / ref.abs().max())
