@@ -226,8 +226,10 @@ __device__ __forceinline__ void head_tail_from_lds16(const HeadTailK& p, unsigne
 // (8+2) x (16+2) input patch - all 64 feature channels (and the 8-channel pc_hm plane pair) in split-bf16 - is copied
 // to LDS once, zero-filled outside the image, and all 9 taps read their B fragments from it at compile-time offsets:
 // no slot table, no barrier and no staging inside the K loop.  A wave owns 64 hidden channels x 128 pixels as 4 x 8
-// accumulators of 16 x 16 (v_mfma_f32_16x16x32_bf16); a k-step is 32 deep = half the channels of one tap (or four
-// taps of the pc_hm plane pair).  Under the chip's power management a dense MFMA loop on random data holds a higher
+// accumulators of 16 x 16 (v_mfma_f32_16x16x32_bf16); a k-step is 32 deep = half the channels of one tap (or ALL nine
+// taps x 3 channels of the pc_hm plane pair, k = 3 tap + channel, read from an operand image built once per workgroup
+// behind the patch - and left out by a workgroup whose pc_hm patch is all zero).  Under the chip's power management a
+// dense MFMA loop on random data holds a higher
 // clock with the 16x16x32 shape than with 32x32x16 at equal cycles per FLOP: measured on this part 1.72 vs 1.51
 // PFLOP/s with every operand re-read from LDS (tools/micro/mfma_shape.hip, MI355X_MICROARCH.md "DVFS give-back"
 // item 7) - and this kernel is bound by exactly that loop.  Weights come as [16-row tile][k32 step][hi|lo][lane][8]
@@ -240,9 +242,17 @@ constexpr int HP_ROWS = (8 + 2) * (16 + 2);    // 180 patch rows (either tile or
 constexpr int HP_PX = 8 * 16;                  // 128 pixels per tile
 constexpr int HP16_RED = 4 * 16 * HP_PX * 4;   // partial sums [wave][16][128] BEHIND the patch
 constexpr int hp16_patch_bytes(bool pc) { return HP_ROWS * (4 * 64 + (pc ? 32 : 0) + 16); }   // 48,960 / 54,720
-// without pc_hm: 48,960 + 32,768 = 81,728 B <= half of the CU's 160 KiB: still two workgroups per CU
+// pc_hm source: behind the patch, the four waves' "my part of the pc_hm patch is non-zero" words (16 B) and the OPERAND IMAGE
+// of the radar k-step, [128 px][hi, lo][32 bf16: k = 3 tap + channel, 27 real] at a row pitch of 80 B (odd multiple of 16)
+constexpr int HP_PCIMG_ROWB = 32 * 2 + 16;
+constexpr int HP_PCIMG = HP_PX * 2 * HP_PCIMG_ROWB;            // 20,480 B
+constexpr int hp16_pc_extra(bool pc) { return pc ? 16 + HP_PCIMG : 0; }
+// without pc_hm: 48,960 + 32,768 = 81,728 B <= half of the CU's 160 KiB: still two workgroups per CU.  With pc_hm and hidden
+// layers: 54,720 + 16 + 20,480 = 75,216 B (the chain's 67,584 B tile reuses it afterwards): two per CU; with pc_hm and no
+// hidden layers 107,984 B: one per CU, as before the image (87,488 B)
 constexpr int hp16_lds(bool pc, bool hidden) {
-  return hidden ? (HT_LDS > hp16_patch_bytes(pc) ? HT_LDS : hp16_patch_bytes(pc)) : hp16_patch_bytes(pc) + HP16_RED;
+  return hidden ? (HT_LDS > hp16_patch_bytes(pc) + hp16_pc_extra(pc) ? HT_LDS : hp16_patch_bytes(pc) + hp16_pc_extra(pc))
+                : hp16_patch_bytes(pc) + hp16_pc_extra(pc) + HP16_RED;
 }
 
 struct HeadPatchK {
@@ -250,7 +260,7 @@ struct HeadPatchK {
   const unsigned char* src[2];               // split-bf16 NHWC sources of the 3x3 layer (feat or its mx rows, pc_hm)
   int src_c[2];
   int H, W, tiles_x, tiles_y, n_ks;
-  int group;                                 // not read (always 0): keeps the kernel argument layout
+  int pc_skip;                               // != 0: a workgroup whose pc_hm patch is all (+-) zero leaves the pc_hm taps out
   int hloop;                                 // consecutive heads one workgroup walks on its patch
   const unsigned char* w_first[CF_MAX_HEADS];
   const float* b_first[CF_MAX_HEADS];
@@ -266,7 +276,8 @@ struct HeadPatchK {
 // every B fragment reads inside segment g (bank-conflict-free ds_read_b128, see colperm below).  Per tap: 2 k-steps of v_mfma_f32_16x16x32_f16 (weights' fp16 hi) and ONE v_mfma_scale_f32_16x16x128_f8f6f4
 // whose four 32-deep K blocks are q6(Wh) . q6(xl) (two 32-channel halves) and q6(Wl) . q6(xh): lane g = l >> 4 of either operand
 // holds K block g, with the block's scale byte in its lane.  Weights stream from L2 in (wave, tap) slabs, two items (of
-// main / main / cross) ahead.  pc_hm stays on bf16x3 with its weights pre-multiplied by 2^(s+4); the accumulators are scaled by
+// main / main / cross) ahead.  pc_hm stays on bf16x3 (one dense k-step, pc_kstep below) with its weights pre-multiplied by
+// 2^(s+4); the accumulators are scaled by
 // first_scale = 2^-(s+4) where the bias is added.  Hidden and output layers: unchanged bf16x3.
 // HID: -1 = n_hidden decided at run time (the bf16x3 instantiations); 0 / 1 = compiled for heads without / with hidden layers
 // (the MX instantiations: the register allocator then sees one of the two epilogues, not both).
@@ -281,7 +292,7 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
   static_assert((T_H + 2) * P_W == HP_ROWS, "both tile shapes have the same patch size");
   constexpr int ROWB = NS * 64 + (PC ? 32 : 0) + 16;     // odd multiple of 16 B
   constexpr int NKF = 9 * NS / 2;                        // k32-steps of the feature channels
-  constexpr int NK = NKF + (PC ? 3 : 0);
+  constexpr int NK = NKF + (PC ? 1 : 0);               // + the radar taps: ONE k-step, k = 3 tap + channel (27 real of 32)
   extern __shared__ __attribute__((aligned(16))) unsigned char xt[];
   const HeadTailK& p = q.t;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: scalar weight tile addressing)
@@ -349,7 +360,13 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       if (row < HP_ROWS) *reinterpret_cast<u32x4*>(xt + row * ROWB + (uu >> 1) * 64 + plane * 32 + (uu & 1) * 16) = v[it];
     }
   }
+  // pc_hm is zero outside the boxes the frustum association painted: a patch (tile + frame) without a non-zero value adds
+  // exact zeros to the accumulators.  Every thread ORs the words it copies (sign bits off: -0 is zero); a wave leaves its
+  // verdict in one word BEHIND the patch (in front of the partial sums / inside the chain's tile, which is written only
+  // after every wave is done with the patch), and the barrier that completes the patch publishes the four words.
+  unsigned* const pc_flags = reinterpret_cast<unsigned*>(xt + hp16_patch_bytes(PC));
   if (PC) {
+    unsigned nz = 0u;
     for (int idx = tid; idx < HP_ROWS * 2; idx += 256) {
       const int row = idx >> 1, plane = idx & 1;
       const int y = y0 - 1 + row / P_W, x = x0 - 1 + row % P_W;
@@ -357,7 +374,10 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       if ((unsigned)y < (unsigned)q.H && (unsigned)x < (unsigned)q.W)
         w = *reinterpret_cast<const u32x4*>(q.src[1] + ((size_t)(b * p.HW + y * q.W + x) * 2 + plane) * q.src_c[1] * 2);
       *reinterpret_cast<u32x4*>(xt + row * ROWB + PC_OFF + plane * 16) = w;
+      nz |= (w[0] | w[1] | w[2] | w[3]) & 0x7fff7fffu;
     }
+    const bool wave_nz = __builtin_amdgcn_ballot_w64(nz != 0u) != 0ull;
+    if (lane == 0) pc_flags[wave] = (wave_nz || !q.pc_skip) ? 1u : 0u;
   }
 
   // B fragment of a 16x16x32 MFMA: lane (g = l >> 4, c = l & 15) holds 8 consecutive channels 8g .. 8g+7 of the
@@ -367,13 +387,65 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
   for (int ct = 0; ct < 8; ++ct)          // pixel ct * 16 + c16: a compile-time stride per ct (immediate offsets of the ds_reads)
     rowb[ct] = ((c16 >> TSH) * P_W + (c16 & TMASK)) * ROWB + ct * ((16 >> TSH) * P_W * ROWB);
   const int koff = (g >> 1) * 64 + (g & 1) * 16;         // 8-channel group inside a 32-channel half (hi plane; lo at +32)
-  int pc_off[3];                             // pc_hm steps: k-group g of step i is tap 4i + g (taps 9..11: zero weights)
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int t = min(4 * i + g, 8);
-    pc_off[i] = ((t / 3) * P_W + t % 3) * ROWB + PC_OFF;
-  }
+  // radar k-step: the same lane reads k = 8g .. 8g+7 of pixel ct * 16 + c16 from the operand image (hi; lo one row on)
+  unsigned char* const pcimg = xt + hp16_patch_bytes(PC) + 16;
+  const int imgb = c16 * (2 * HP_PCIMG_ROWB) + g * 16;
   __syncthreads();                           // the patch is complete
+  bool pc_live = false;                      // workgroup-uniform: the pc_hm taps contribute
+  if (PC) {
+    const u32x4 f = *reinterpret_cast<const u32x4*>(pc_flags);
+    pc_live = __builtin_amdgcn_readfirstlane((int)(f[0] | f[1] | f[2] | f[3])) != 0;
+  }
+  if (PC && pc_live) {
+    // the operand image, once per workgroup: thread = (pixel, plane) gathers channels 0-2 of its 9 taps from the patch's
+    // pc_hm planes (outside the image: the patch's zeros) into one row, k = 3 tap + channel, k = 27..31 zero
+    const int ipx = tid & (HP_PX - 1), plane = tid >> 7;
+    const unsigned char* sp = xt + ((ipx >> TSH) * P_W + (ipx & TMASK)) * ROWB + PC_OFF + plane * 16;
+    unsigned e[32];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const u32x2 w = *reinterpret_cast<const u32x2*>(sp + ((t / 3) * P_W + t % 3) * ROWB);
+      e[3 * t] = w[0] & 0xffffu;
+      e[3 * t + 1] = w[0] >> 16;
+      e[3 * t + 2] = w[1] & 0xffffu;
+    }
+#pragma unroll
+    for (int k = 27; k < 32; ++k) e[k] = 0u;
+    unsigned char* dp = pcimg + (ipx * 2 + plane) * HP_PCIMG_ROWB;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      *reinterpret_cast<u32x4*>(dp + j * 16) = u32x4{e[8 * j] | (e[8 * j + 1] << 16), e[8 * j + 2] | (e[8 * j + 3] << 16),
+                                                     e[8 * j + 4] | (e[8 * j + 5] << 16), e[8 * j + 6] | (e[8 * j + 7] << 16)};
+    __syncthreads();                         // (workgroup-uniform branch) the image is complete
+  }
+  // the radar k-step on bf16x3 (cross, cross, main as everywhere): 4 row tiles x 8 pixel tiles x 3 = 96 MFMAs
+  auto pc_kstep = [&](const bf16x8 (&ah)[4], const bf16x8 (&al)[4], f32x4 (&acc)[4][8]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      bf16x8 xh[4], xl[4];
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const unsigned char* r = pcimg + imgb + (4 * hf + ct) * (16 * 2 * HP_PCIMG_ROWB);
+        xh[ct] = *reinterpret_cast<const bf16x8*>(r);
+        xl[ct] = *reinterpret_cast<const bf16x8*>(r + HP_PCIMG_ROWB);
+      }
+#pragma unroll
+      for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct)
+          acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[rt], xh[ct], acc[rt][4 * hf + ct], 0, 0, 0);
+#pragma unroll
+      for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct)
+          acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt], xl[ct], acc[rt][4 * hf + ct], 0, 0, 0);
+#pragma unroll
+      for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct)
+          acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt], xh[ct], acc[rt][4 * hf + ct], 0, 0, 0);
+    }
+  };
   auto first_layer = [&](int head, f32x4 (&acc)[4][8]) __attribute__((always_inline)) {
   if constexpr (MX) {
     const unsigned char* wb = q.w_first[head] + (size_t)wave * (9 * MX_SLAB);
@@ -393,6 +465,22 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(wb + tap * MX_SLAB), 0, MX_SLAB, 0x00020000);
     };
     const int l16 = lane * 16, l8 = lane * 8, l4 = lane * 4;
+    // radar k-step (PC): behind the slabs the pc_hm weights x 2^s x feat_scale lie in the container [wv 4][ks 3][rt 4][hi, lo][lane 64]
+    // [8 bf16] of the per-tap layout; the dense k-step (k = 3 tap + channel, lane group G = k >> 3) is threaded through its
+    // padding - group 0 in the g = 0 lanes of k-step 0, groups 1-3 in the g = 1..3 lanes of k-step 2 (packing.pack_head_first_mx) -
+    // so a lane's fragment is at lane * 16 (+ two k-steps for G > 0).  With hidden layers (HID == 1, the model's radar heads) the 8
+    // fragments are requested inside tap 8, where a tap 9's main fragments would be: those registers are free by then, and no L2
+    // latency is exposed in front of the k-step.  Without hidden layers the epilogue's addresses are live across the head loop
+    // and the early request costs scratch: requested where they are used.
+    bf16x8 ph[4], pl[4];
+    auto ldp = [&](bf16x8 (&d)[4], int plane) {
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<unsigned char*>(q.w_first[head] + (size_t)4 * 9 * MX_SLAB), 0, 4 * 3 * 4 * 2048, 0x00020000);
+      const int lo = l16 + (g ? 2 * 4 * 2048 : 0);
+#pragma unroll
+      for (int rt = 0; rt < 4; ++rt)
+        d[rt] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, lo, wave * (3 * 4 * 2048) + rt * 2048 + plane * 1024, 0));
+    };
     auto ldm = [&](hf16x8 (&d)[4], int tap, int ks2) {
       const __amdgpu_buffer_rsrc_t rs = slab(tap);
 #pragma unroll
@@ -485,43 +573,22 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       main_half(am[0], o0, 1);
       main_half(am[1], o1, 0);
       if (tap + 1 < 9) CF_MX_LD(ldm(am[0], tap + 1, 0));
+      else if (PC && HID == 1) ldp(ph, 0);
       __builtin_amdgcn_sched_barrier(0);
       main_half(am[1], o1, 1);
       cross_pair(toff, 0);
       cross_pair(toff, 1);
       if (tap + 1 < 9) CF_MX_LD(ldm(am[1], tap + 1, 1));
+      else if (PC && HID == 1) ldp(pl, 1);
       __builtin_amdgcn_sched_barrier(0);
       cross_pair(toff, 2);
       cross_pair(toff, 3);
     }
     __builtin_amdgcn_sched_barrier(0);       // (the epilogue's loads stay behind the last item)
-    if (PC) {                                // pc_hm on bf16x3: 3 k-steps of 4 taps x 8 channels, weights x 2^(s+4)
-      const unsigned char* wp = q.w_first[head] + (size_t)4 * 9 * MX_SLAB + (size_t)wave * (3 * 4 * 2048);
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        bf16x8 ph[4], pl[4];
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt) {
-          ph[rt] = *reinterpret_cast<const bf16x8*>(wp + (i * 4 + rt) * 2048 + (unsigned)lane * 16u);
-          pl[rt] = *reinterpret_cast<const bf16x8*>(wp + (i * 4 + rt) * 2048 + 1024 + (unsigned)lane * 16u);
-        }
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-          bf16x8 xh[4], xl[4];
-#pragma unroll
-          for (int ct = 0; ct < 4; ++ct) {
-            xh[ct] = *reinterpret_cast<const bf16x8*>(xt + rowb[4 * hf + ct] + pc_off[i]);
-            xl[ct] = *reinterpret_cast<const bf16x8*>(xt + rowb[4 * hf + ct] + pc_off[i] + 16);
-          }
-#pragma unroll
-          for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) {
-              acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pl[rt], xh[ct], acc[rt][4 * hf + ct], 0, 0, 0);
-              acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph[rt], xl[ct], acc[rt][4 * hf + ct], 0, 0, 0);
-              acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph[rt], xh[ct], acc[rt][4 * hf + ct], 0, 0, 0);
-            }
-        }
+    if (PC) {
+      if (pc_live) {                         // (an all-zero pc_hm patch would add exact zeros)
+        if constexpr (HID != 1) { ldp(ph, 0); ldp(pl, 1); }
+        pc_kstep(ph, pl, acc);
       }
     }
     return;
@@ -545,17 +612,10 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
   load_w(wh[0], wl[0], 0);
 
 #pragma unroll
-  for (int ks = 0; ks < NK; ++ks) {
+  for (int ks = 0; ks < NKF; ++ks) {
     if (ks + 1 < NK) load_w(wh[(ks + 1) & 1], wl[(ks + 1) & 1], ks + 1);
-    int off, lo;
-    if (ks < NKF) {
-      const int tap = ks / (NS / 2), half = ks % (NS / 2);
-      off = ((tap / 3) * P_W + tap % 3) * ROWB + half * 128 + koff;
-      lo = 32;
-    } else {
-      off = pc_off[ks - NKF < 3 ? ks - NKF : 0];
-      lo = 16;
-    }
+    const int tap = ks / (NS / 2), half = ks % (NS / 2);
+    const int off = ((tap / 3) * P_W + tap % 3) * ROWB + half * 128 + koff, lo = 32;
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {         // tile rows 0-3, then 4-7: half of the B fragments live at a time
       bf16x8 xh[4], xl[4];
@@ -581,6 +641,9 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
           acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks & 1][rt], xh[ct], acc[rt][4 * hf + ct], 0, 0, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
+  }
+  if (PC) {                                  // the radar k-step, or (all-zero pc_hm patch: exact zeros) nothing - see the MX form
+    if (pc_live) pc_kstep(wh[NKF & 1], wl[NKF & 1], acc);
   }
   };
 
@@ -665,7 +728,7 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
   }
   continue;
 #endif
-  float* red = reinterpret_cast<float*>(xt + hp16_patch_bytes(PC));   // [wave][n 16][px 128], BEHIND the patch (which the next head reuses)
+  float* red = reinterpret_cast<float*>(xt + hp16_patch_bytes(PC) + hp16_pc_extra(PC));   // [wave][n 16][px 128], BEHIND the patch (which the next head reuses)
 #pragma unroll
   for (int ct = 0; ct < 8; ++ct)
 #pragma unroll
@@ -808,17 +871,17 @@ extern "C" int cf_head_fused(const cf_head_fused_args* a, void* stream) {
     cf_set_error(CF_HEAD_FORMS ": there is no slot-table kernel (layout3x3 = 0)");
     return CF_EINVAL;
   }
-  // K order = 9 taps x 64 feature channels [, then the pc_hm taps four at a time]
+  // K order = 9 taps x 64 feature channels [, then ONE k-step of the pc_hm taps: k = 3 tap + channel]
   const bool m16 = a->mfma16 != 0;           // fragments packed for v_mfma_f32_16x16x32_bf16 (k-steps of 32)
   hp.H = H; hp.W = W;
   hp.n_ks = a->K_pad / 32;
-  CF_REQUIRE(mx || a->K_pad / 16 >= (a->n_src == 2 ? 41 : 36), "cf_head_fused: K_pad=%d too small for the 3x3 layout", a->K_pad);
+  CF_REQUIRE(mx || a->K_pad / 16 >= (a->n_src == 2 ? 38 : 36), "cf_head_fused: K_pad=%d too small for the 3x3 layout", a->K_pad);
   for (int i = 0; i < n_heads; ++i) {
     CF_REQUIRE(!mx || (a->first_scale[i] > 0.0f && a->first_scale[i] < 1e30f), "cf_head_fused: head %d: first_scale missing (mx)", i);
     hp.first_scale[i] = a->first_scale[i];
   }
   if (m16) {
-    CF_REQUIRE(mx || (a->K_pad % 32 == 0 && a->K_pad / 32 >= (a->n_src == 2 ? 21 : 18)), "cf_head_fused: K_pad=%d (16x16x32 fragments)", a->K_pad);
+    CF_REQUIRE(mx || (a->K_pad % 32 == 0 && a->K_pad / 32 >= (a->n_src == 2 ? 19 : 18)), "cf_head_fused: K_pad=%d (16x16x32 fragments)", a->K_pad);
     for (int i = 0; i < n_heads; ++i)
       CF_REQUIRE(a->tail.n_out[i] <= 16, "cf_head_fused: head %d: n_out=%d > 16 (the 16x16x32 kernels produce ONE 16-row output tile, with or without hidden layers)", i, a->tail.n_out[i]);
   }
@@ -833,6 +896,10 @@ extern "C" int cf_head_fused(const cf_head_fused_args* a, void* stream) {
   CF_REQUIRE(m16, CF_HEAD_FORMS ": nothing reads 32x32x16 fragments (mfma16 = 0)");
   bool portrait = t_port < t_land;
   if (const char* e = getenv("CF_HEAD_TILE")) portrait = atoi(e) != 0;
+  // workgroups whose pc_hm patch is all zero leave the pc_hm taps out (results do not depend on it; CF_HEAD_PC_SKIP = 0
+  // runs them everywhere, for dev tools and tests)
+  hp.pc_skip = 1;
+  if (const char* e = getenv("CF_HEAD_PC_SKIP")) hp.pc_skip = atoi(e) != 0;
   hp.tiles_x = portrait ? (W + 7) / 8 : (W + 15) / 16;
   hp.tiles_y = portrait ? (H + 15) / 16 : (H + 7) / 8;
   // heads without hidden layers: a workgroup walks several heads on one patch (chosen below; CF_HEAD_LOOP overrides

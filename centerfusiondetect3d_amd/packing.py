@@ -102,7 +102,10 @@ def pack_conv(weight, bias, sources: Sequence[Source], stride=1, pad=None, dilat
 def pack_conv_bf16(weight, bias, sources: Sequence[Source], stride=1, pad=None, dilation=1, fragments=16) -> PackedConv:
     """Packing of a head's first layer for cf_head_fused: slots of 8 channels in the canonical order (source, tap, channel
     group), weights split as w = hi + lo (hi = rne(w), lo = rne(w - hi)) into bf16 planes and laid out as 16x16x32 MFMA
-    fragments (pack_fragments16; fragments = 16 is the only form).  Source.stride = channels per plane."""
+    fragments (pack_fragments16; fragments = 16 is the only form).  Source.stride = channels per plane.
+    A SECOND source whose taps fit one k-step (9 * channels <= 32: the 3-channel pc_hm planes) is packed DENSE: one 32-deep
+    chunk with k = channels * tap + channel (27 real, the rest zero), which the kernel meets with the operand image it builds
+    in LDS; the chunk's four slots are padding entries (the slot table cannot spell that order, and the kernel reads none)."""
     assert fragments == 16, "cf_head_fused reads 16x16x32 fragments only"
     co, ci, kh, kw = weight.shape
     assert ci == sum(s.channels for s in sources), (ci, [s.channels for s in sources])
@@ -111,6 +114,12 @@ def pack_conv_bf16(weight, bias, sources: Sequence[Source], stride=1, pad=None, 
     slots, cols, c_lo = [], [], 0
     for si, s in enumerate(sources):
         assert s.stride % 8 == 0 and s.c_base % 8 == 0
+        if si > 0 and kh * kw * s.channels <= 32:
+            for j in range(4):
+                slots.append([si, 0, 0, -1])
+                cols.append(("dense", c_lo, s.channels, 0) if j == 0 else (-1, 0, 0, 0))
+            c_lo += s.channels
+            continue
         per_tap = (s.channels + 7) // 8
         n_slots = 0
         for r in range(kh):
@@ -132,7 +141,9 @@ def pack_conv_bf16(weight, bias, sources: Sequence[Source], stride=1, pad=None, 
     w = torch.zeros(n_pad, k_pad)
     wf = weight.float()
     for j, (c0, real, r, q) in enumerate(cols):
-        if real:
+        if c0 == "dense":                  # (c0, first channel, channels): k = channels * tap + channel
+            w[:co, 8 * j:8 * j + kh * kw * r] = wf[:, real:real + r].permute(0, 2, 3, 1).reshape(co, kh * kw * r)
+        elif real:
             w[:co, 8 * j:8 * j + real] = wf[:, c0:c0 + real, r, q]
     b = torch.zeros(n_pad)
     b[:co] = bias
@@ -468,8 +479,13 @@ def pack_head_first_mx(weight, bias, pc: bool, feat_scale: float = 16.0):
         [rt 4]([lane 64][16 B] | [lane 64][8 B])   cross term, 24 B per lane = 32 FP6 fields: g = 0, 1: q6(Wh) channels
                                         32 g .. +32 (to meet q6(xl)); g = 2, 3: q6(Wl) channels 32 (g - 2) .. +32 (to meet q6(xh))
         [lane 64][4 B]                  E8M0 scale bytes of that lane's block, byte rt
-    then (pc only) the pc_hm part as bf16x3 fragments of W * 2^s * feat_scale: [wv 4][ks 3][rt 4][hi, lo][lane 64][8 bf16], k-step ks =
-    taps 4 ks .. 4 ks + 3 x 8 channels (3 real)."""
+    then (pc only) the pc_hm part as bf16x3 fragments of W * 2^s * feat_scale in the container [wv 4][ks 3][rt 4][hi, lo][lane 64][8 bf16]
+    (4 * 3 * 4 * 2048 bytes; the stream's length and these positions are what earlier readers of it decode), holding two things:
+      * per tap, as always: lane (g, i) of k-step ks carries tap 4 ks + g, channels 0-2 in elements 0-2, for row 64 wv + 16 rt + i;
+      * threaded through that layout's padding, the ONE dense k-step the kernel multiplies: k = 3 tap + channel (27 real values,
+        k = 27..31 zero), lane group G of the fragment holding k = 8 G + j.  Group 0 sits in the g = 0 lanes of k-step 0 (its elements
+        0-2 are tap 0's channels in both readings, elements 3-7 were padding), groups 1-3 in the g = 1..3 lanes of k-step 2 (the
+        padding taps 9-11).  The kernel reads nothing else of this part: a lane's fragment is at lane * 16 + (G ? 2 * 4 * 2048 : 0)."""
     co, ci, kh, kw = weight.shape
     assert co == 256 and (kh, kw) == (3, 3) and ci == (67 if pc else 64)
     w = weight.double()
@@ -495,10 +511,15 @@ def pack_head_first_mx(weight, bias, pc: bool, feat_scale: float = 16.0):
     if pc:
         wp = torch.zeros(256, 12, 8, dtype=torch.float64)                               # (row, tap (9 real), 8 ch (3 real))
         wp[:, :9, :3] = (w[:, 64:67] * 2.0 ** s_exp * float(feat_scale)).permute(0, 2, 3, 1).reshape(256, 9, 3)
-        wp = wp.float().view(256, 3, 32)                                                # k-step ks: k = 8 (tap - 4 ks) + c
-        ph = wp.to(torch.bfloat16)
-        pl = (wp - ph.float()).to(torch.bfloat16)
-        f = torch.stack([ph, pl], 0).view(2, 4, 4, 16, 3, 4, 8).permute(1, 4, 2, 0, 5, 3, 6).contiguous()   # wv, ks, rt, plane, g, i, j
+        wp = wp.float()
+        wd = torch.zeros(256, 32)                                                       # (row, k = 3 tap + c: 27 real)
+        wd[:, :27] = wp[:, :9, :3].reshape(256, 27)
+        split = lambda t: torch.stack([t.to(torch.bfloat16), (t - t.to(torch.bfloat16).float()).to(torch.bfloat16)], 0)
+        f = split(wp.view(256, 3, 32)).view(2, 4, 4, 16, 3, 4, 8).permute(1, 4, 2, 0, 5, 3, 6).contiguous()   # wv, ks, rt, plane, g, i, j
+        d = split(wd).view(2, 4, 4, 16, 4, 8).permute(1, 2, 0, 4, 3, 5)                  # wv, rt, plane, G, i, j
+        assert torch.equal(f[:, 0, :, :, 0, :, :3], d[:, :, :, 0, :, :3])               # tap 0 = k 0..2 in both readings
+        f[:, 0, :, :, 0] = d[:, :, :, 0]
+        f[:, 2, :, :, 1:] = d[:, :, :, 1:]
         parts.append(f.view(torch.uint8).reshape(-1))
     b = torch.zeros(256)
     b[:co] = bias.float()

@@ -263,6 +263,11 @@ typedef struct cf_head_tail_args {
  * hidden-map round trips through HBM).
  * src[]: split-bf16 NHWC sources (feat, 64 channels [, pc_hm, 8 channels]); w_first[i]: 16x16x32 fragments
  * [256/16][K_pad/32] of head i in the canonical 3x3 slot order (packing.pack_conv_bf16); b_first[i]: 256 floats.
+ * The pc_hm source (3 real channels) takes ONE k-step behind the 18 of the feature channels, k = 3 tap + channel (27 real,
+ * k = 27..31 zero weights): the kernel gathers the matching operand rows from the pc_hm planes of its LDS patch.  A workgroup
+ * whose pc_hm patch (tile + 1-pixel frame) holds only +-0 leaves that k-step out - it would add exact zeros; the environment
+ * variable CF_HEAD_PC_SKIP = 0 runs it everywhere (dev switch, results are the same bits).  (layout of that k-step changed
+ * within ABI 7: the argument block and the exports did not; w_first[] is whatever packing.py of the same tree writes)
  * ONE form runs: layout3x3 = 1 with mfma16 = 1 (mx = 0 or 1).  The fields can still spell the forms of earlier kernels
  * (layout3x3 = 0: an arbitrary slot table; mfma16 = 0: 32x32x16 fragments): those calls return CF_EINVAL. */
 typedef struct cf_head_fused_args {
@@ -271,12 +276,13 @@ typedef struct cf_head_fused_args {
   int32_t src_c[2];
   int32_t n_src;
   const cf_slot* slots;                    /* mx = 0: validated as before (non-NULL; 8-channel slots), not read by the kernel */
-  int32_t K_pad;                           /* mx = 0: validated as before - a multiple of 64, <= 2048, >= 576 (672 with pc_hm) */
+  int32_t K_pad;                           /* mx = 0: validated as before - a multiple of 64, <= 2048, >= 576 (608 with pc_hm: 18 + 1 k-steps) */
   const void* w_first[CF_MAX_HEADS];
   const float* b_first[CF_MAX_HEADS];
   int32_t layout3x3;                       /* must be 1: the slot order is the canonical one - src[0] (64 channels): 9 taps
-                                              x 8 slots, then src[1] (8 channels): 9 taps x 1 slot - which the 2-D patch
-                                              kernel implies (no slot table reads)                                       */
+                                              x 8 slots, then src[1] (8 channels, 3 real): one dense 32-deep chunk, k = 3 tap +
+                                              channel (its 4 slots are padding entries) - which the 2-D patch kernel implies
+                                              (no slot table reads)                                                       */
   const void* w_out_perm[CF_MAX_HEADS];    /* n_hidden == 0: w_out as ONE 16-row tile whose k position (step ks, group g, j) holds
                                               hidden channel 64 (ks >> 1) + 16 (2 (ks & 1) + (j >> 2)) + 4 g + (j & 3) - the order of
                                               an accumulator register group (packing.pack_fragments16(acc_order=True))    */
@@ -287,8 +293,10 @@ typedef struct cf_head_fused_args {
                                               cross terms" (v_mfma_f32_16x16x32_f16 + v_mfma_scale_f32_16x16x128_f8f6f4, 1.5 passes per
                                               product instead of 3): src[0] is the 272-byte-per-pixel image cf_pack_feat_mx writes
                                               (src_c[0] = 64), w_first[i] the operand stream of packing.pack_head_first_mx (slots / K_pad
-                                              are not read), src[1] (optional) the split-bf16 pc_hm planes as before; the tail layers are
-                                              unchanged.  ABI 4 */
+                                              are not read; 4 * 9 * 14592 bytes of (wave, tap) slabs, then with src[1] 4 * 3 * 4 * 2048 bytes:
+                                              the pc_hm weights per tap as before, with the dense pc_hm k-step threaded through that layout's
+                                              padding - packing.pack_head_first_mx), src[1] (optional) the
+                                              split-bf16 pc_hm planes as before; the tail layers are unchanged.  ABI 4 */
   float first_scale[CF_MAX_HEADS];         /* mx: 2^-(s+4) of head i's first layer (applied where b_first is added) */
 } cf_head_fused_args;
 int cf_head_fused(const cf_head_fused_args* a, void* stream);
