@@ -16,8 +16,48 @@ CASES = [(1, 32, 27, 5, 7, 1.0, True),       # one chunk, N not a multiple of an
          (2, 32, 64, 17, 21, 8.0, True),     # samples far outside every border, partial tiles in both directions
          (1, 128, 32, 8, 40, 3.0, True),     # wide row, four chunks
          (2, 64, 64, 9, 13, 2.0, False),     # mask=None: its gradient is None, the others as for a mask of ones
-         (1, 160, 192, 6, 9, 2.0, True)]     # five chunks (a wave of the data kernel takes two), two groups of output tiles (the second partial)
+         (1, 160, 192, 6, 9, 2.0, True),     # five chunks (a wave of the data kernel takes two), two groups of output tiles (the second partial)
+         # ---- the launch-size branches of csrc/cf_dcn_bwd.hip (NEW_CASES below; the geometry each one is there for is asserted, not
+         # claimed: SLAB_GEOMETRY, tests/test_dcn_backward_cpu.py) ----
+         (1, 512, 256, 7, 9, 2.0, True),     # 16 chunks, four per wave; N = 256: dynamic LDS at its 32768-byte floor, two full output groups; partial 32-pixel tile
+         (1, 512, 256, 35, 53, 2.0, True),   # smallest map on which the slab cap binds for 512 -> 256; odd slab length rounded up, short last slab
+         (1, 512, 256, 61, 89, 2.0, True),   # that layer's training slab length: about 800 pixels summed in one accumulator chain
+         (1, 64, 64, 116, 250, 2.0, True),   # the 64 -> 64 cap: 113 slabs through the reduce kernel, M just above 113 * 256
+         (1, 256, 128, 6, 11, 3.0, True),    # channel pair of the network
+         (2, 128, 128, 5, 9, 2.0, False),    # channel pair of the network, mask=None
+         (1, 256, 64, 9, 7, 30.0, True),     # channel pair of the network, offsets far outside
+         (1, 64, 320, 5, 6, 2.0, True),      # N > 256: the data kernel's LDS limit raised above 64 KB; three output groups, the last half full
+         (1, 32, 1024, 3, 5, 2.0, True)]     # the largest N the entry points accept: 156,672 B of LDS
+NEW_CASES = range(6, len(CASES))             # their gates come from the fp32 oracle at test time (case_gates of the GPU test)
 EPS = 1e-3
+
+# (slabs, cap, pixels per slab, pixels of the last slab) of the weight gradient, per case index: what slab_geometry() must give
+SLAB_GEOMETRY = {6: (1, 7, 64, 63), 7: (7, 7, 266, 259), 8: (7, 7, 776, 773), 9: (113, 113, 258, 104), 10: (1, 28, 66, 66),
+                 11: (1, 56, 90, 90), 12: (1, 28, 64, 63), 13: (1, 37, 30, 30), 14: (1, 28, 16, 15)}
+
+
+# ---- the launch geometry of csrc/cf_dcn_bwd.hip, restated (bwd_tiles_per_wave, bwd_slabs, the slab length of
+# cf_dcn_v2_bwd_weight, the LDS of cf_dcn_v2_bwd_data); tests/test_dcn_backward_cpu.py holds the slab count against the library's ----
+def tiles_per_wave(N):
+    return 1 if N <= 32 else 2 if N <= 64 else 4
+
+
+def slab_geometry(M, C, N):
+    """-> (slabs, cap, slab_px, pixels of the last slab) for M = B*H*W pixels, C input and N output channels"""
+    nt = tiles_per_wave(N)
+    per_slab = 9 * (C // 32) * ((N + 32 * nt - 1) // (32 * nt))
+    cap = max(2048 // per_slab, 1)
+    slabs = max(min((M + 255) // 256, cap), 1)
+    slab_px = (M + slabs - 1) // slabs
+    slab_px += slab_px & 1
+    return slabs, cap, slab_px, M - (slabs - 1) * slab_px
+
+
+def data_kernel_geometry(C, N):
+    """-> (chunks per wave, dynamic LDS bytes, static + dynamic LDS bytes) of the data kernel"""
+    chunks, waves = C // 32, min(C // 32, 4)
+    dyn = (N + 1) // 2 * 256
+    return (chunks + waves - 1) // waves, dyn, 9 * 32 * 2 * 16 + 4 * 32 * 32 * 4 + dyn
 
 
 def rnd(*shape, seed=0, scale=1.0):
@@ -70,6 +110,17 @@ def oracle_grads(x, off, w, b, mask, R, dtype=torch.float64):
 
 def relerr(got, ref):
     return float((got.double() - ref.double()).abs().max() / ref.double().abs().max().clamp_min(1e-300))
+
+
+BASE_GATE, CEILING = 5e-6, 1.25e-5
+
+
+def case_gate(e32):
+    """the gate of one gradient of one of NEW_CASES from the fp32 oracle's own error on it: the project's 5e-6 while that error is
+    below half of it, otherwise twice the error (the kernel's summation order is one more fp32 order, nothing else); above the
+    ceiling the case measures nothing and is refused"""
+    assert e32 <= CEILING, f"fp32 oracle error {e32:.2e} above {CEILING:.2e}: the case is unusable"
+    return BASE_GATE if e32 < BASE_GATE / 2 else 2 * e32
 
 
 # ---- the reference's DeformConv call sequence (dla.py:456-472) with a loss behind it ----

@@ -28,6 +28,11 @@ CASES = [
     ("dense_unc_mask0", (2, 10, 16, 24, 32), "middle", True, True, True),
     ("dense_camera", (2, 10, 16, 24, 32), "camera", False, True, False),
     ("dense_early", (2, 10, 16, 24, 32), "early", False, True, False),
+    # R = B * M = 1280 rows on 221 pixels: the object kernel's 1024-thread loops run twice, many colliding atomic adds in the backward
+    ("manyrows", (5, 10, 13, 17, 256), "middle", True, True, False),
+    # 1,075,200 heat-map elements: just above the 1,048,576 at which the dense passes' 1024-workgroup cap binds (grid-stride loops
+    # run twice, all 1024 partial sums enter the object kernel)
+    ("bigmap", (3, 10, 160, 224, 128), "middle", False, True, False),
 ]
 NAMES = [c[0] for c in CASES]
 

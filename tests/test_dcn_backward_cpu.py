@@ -77,3 +77,34 @@ def test_dcn_bwd_entry_points_validate_without_a_gpu():
     n = lib.cf_dcn_v2_bwd_workspace_bytes(1, 4, 4, 32, 8)
     assert n >= (9 * 8 * 32 + 8) * 4 and n % ((9 * 8 * 32 + 8) * 4) == 0
     assert lib.cf_dcn_v2_bwd_workspace_bytes(0, 4, 4, 32, 8) == 0
+
+
+def test_new_cases_reach_the_launch_size_branches_they_are_there_for():
+    """the comments on the cases of tests/dcn_backward_ref.py, as assertions: the restated slab geometry of every case added for
+    a launch-size branch is the one listed, and the restatement's slab count is the library's (its workspace size says it)"""
+    from centerfusiondetect3d_amd import _lib
+    from tests import dcn_backward_ref as T
+    lib = _lib.load()
+    assert sorted(T.SLAB_GEOMETRY) == list(T.NEW_CASES)
+    for i, (B, C, N, H, W, _, _) in enumerate(T.CASES):
+        slabs = T.slab_geometry(B * H * W, C, N)[0]
+        assert lib.cf_dcn_v2_bwd_workspace_bytes(B, H, W, C, N) == slabs * (9 * N * C + N) * 4, T.CASES[i]
+    for i in T.NEW_CASES:
+        B, C, N, H, W, _, _ = T.CASES[i]
+        slabs, cap, slab_px, last = geo = T.slab_geometry(B * H * W, C, N)
+        assert geo == T.SLAB_GEOMETRY[i], (T.CASES[i], geo)
+        assert slab_px % 2 == 0 and 0 < last <= slab_px and (slabs - 1) * slab_px + last == B * H * W
+    old = [T.slab_geometry(B * H * W, C, N) for B, C, N, H, W, _, _ in T.CASES[:6]]
+    assert max(g[0] for g in old) == 3 and all(g[0] < g[1] for g in old)          # the cap never bound before
+    for i in (7, 8, 9):                                                            # the cap binds: fewer slabs than 256-pixel ones
+        B, C, N, H, W, _, _ = T.CASES[i]
+        slabs, cap, _, _ = T.SLAB_GEOMETRY[i]
+        assert slabs == cap < (B * H * W + 255) // 256
+    assert -(-35 * 53 // 7) % 2 == 1                                               # (35,53): an odd length, rounded up
+    assert 113 * 256 < 116 * 250 <= 114 * 256                                      # (116,250): one 256-pixel slab more than the cap
+    # the data kernel: chunks per wave, dynamic LDS against the 32768-byte floor and the 64 KB default, the most that fits
+    assert max(T.data_kernel_geometry(C, N)[0] for _, C, N, _, _, _, _ in T.CASES[:6]) == 2
+    assert T.data_kernel_geometry(512, 256) == (4, 32768, 58368)
+    assert T.data_kernel_geometry(64, 320)[2] == 66560 > 65536
+    assert T.data_kernel_geometry(32, 1024)[2] == 156672 <= 163840
+    assert all((B * H * W) % 32 for B, _, _, H, W, _, _ in (T.CASES[6], T.CASES[13], T.CASES[14]))     # partial 32-pixel tiles

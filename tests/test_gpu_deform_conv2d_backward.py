@@ -22,9 +22,32 @@ The gates.  The project's forward gate is 5e-6.  The same backward through the o
     (1,160,192,6,9,2)                3.1e-07   3.7e-07   3.4e-07   1.2e-07   4.0e-07
     worst                            1.4e-06   1.6e-06   1.1e-06   1.2e-07   1.8e-06
 
-Every gradient's fp32-oracle error is below 2.5e-6 on every case, so every gate is 5e-6 (the rule: 5e-6 where the fp32 oracle
-meets 2.5e-6 everywhere, otherwise twice its worst error - twice because the kernel's summation order, atomics and the K
-split, is another fp32 order than the CPU's, and nothing more).
+Every gradient's fp32-oracle error is below 2.5e-6 on every one of these six cases, so their gate is 5e-6 (the rule: 5e-6 where
+the fp32 oracle meets 2.5e-6 everywhere, otherwise twice its worst error - twice because the kernel's summation order, atomics
+and the K split, is another fp32 order than the CPU's, and nothing more).
+
+The cases after them (NEW_CASES of tests/dcn_backward_ref.py) are there for the branches csrc/cf_dcn_bwd.hip picks from the
+problem size - the slab cap of the weight gradient, the reduce kernel over many slabs, four chunks per wave of the data kernel,
+its dynamic LDS at the 32768-byte floor, above 64 KB and at the most N = 1024 takes; tests/test_dcn_backward_cpu.py asserts the
+geometry each one reaches.  The same rule holds for them per case and per gradient, from the fp32 oracle run on the CPU at test
+time (`case_gates`; both numbers are printed before the operator runs): 5e-6 while the fp32 oracle's own error on that case and
+gradient is below 2.5e-6, otherwise twice that error; above 1.25e-5 the case fails as unusable.  Measured by the same tool:
+
+    case (B,Cin,Cout,H,W,scale)      gx        goffset   gw        gbias     gmask
+    (1,512,256,7,9,2)                4.5e-07   2.3e-07   4.3e-07   1.4e-07   4.1e-07
+    (1,512,256,35,53,2)              1.8e-06   1.9e-06   1.7e-06   1.5e-07   2.6e-06
+    (1,512,256,61,89,2)              3.6e-06   4.5e-06   2.9e-06   1.3e-07   5.0e-06
+    (1,64,64,116,250,2)              8.1e-06   8.9e-06   6.7e-06   1.6e-07   9.0e-06
+    (1,256,128,6,11,3)               4.9e-07   5.3e-07   3.6e-07   8.1e-08   7.6e-07
+    (2,128,128,5,9,2) mask=None      3.6e-07   3.6e-07   3.5e-07   8.6e-08   -
+    (1,256,64,9,7,30)                1.9e-07   2.2e-07   2.0e-07   6.3e-08   2.4e-07
+    (1,64,320,5,6,2)                 4.5e-07   4.0e-07   3.3e-07   7.5e-08   4.6e-07
+    (1,32,1024,3,5,2)                4.3e-07   3.8e-07   1.9e-07   1.7e-07   3.3e-07
+
+On the three large maps the fp32 oracle is above 2.5e-6 for a known reason: a sampling coordinate near 250 carries an fp32
+rounding of about 1.5e-5 in its fractional part, and the kernel commits the same rounding.  So their gates are up to 1.8e-5
+(gx / goffset / gw / gmask of the 116 x 250 map: 1.6e-5 / 1.8e-5 / 1.3e-5 / 1.8e-5); gbias is 5e-6 everywhere.  The fp32 sums
+depend on the CPU's thread count in the last digit, so a gate computed at test time can differ from this table by a few per cent.
 
 The call-sequence test (cases, helpers and the graph itself: tests/dcn_backward_ref.py) runs torch's own GPU convolution, batch
 norm and their backward around the operator.  The same graph on the oracle in fp32 on the CPU, against float64:
@@ -44,8 +67,8 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from oracle import dcn_ref
-from tests.dcn_backward_ref import (CASES, NAMES, S, P, D, SEQ_NAMES, SEQ_SHAPE, integer_distance, make_case, oracle_grads,
-                                    relerr, rnd, sequence_grads)
+from tests.dcn_backward_ref import (CASES, NAMES, NEW_CASES, S, P, D, SEQ_NAMES, SEQ_SHAPE, case_gate, integer_distance, make_case,
+                                    oracle_grads, relerr, rnd, sequence_grads)
 
 GATE = {"gx": 5e-6, "goffset": 5e-6, "gmask": 5e-6, "gw": 5e-6, "gbias": 5e-6}
 SEQ_GATE = 1e-5
@@ -72,22 +95,37 @@ def reference(i):
     return oracle_grads(*make_case(i))
 
 
-def check(tag, got, ref, names):
+@functools.lru_cache(maxsize=None)
+def case_gates(i):
+    """the gates of case i.  The first six: GATE.  One of NEW_CASES: per gradient, from the fp32 oracle's own error against float64
+    on that case, computed here on the CPU and printed (tests/dcn_backward_ref.case_gate); nothing of the kernel enters it"""
+    if i not in NEW_CASES:
+        return dict(GATE)
+    g32, ref = oracle_grads(*make_case(i), dtype=torch.float32), reference(i)
+    e32 = {n: relerr(g32[n], ref[n]) for n in NAMES if ref[n] is not None}
+    print(f"[deform_conv2d backward] {CASES[i]}: fp32 oracle " + "  ".join(f"{n} {e:.2e}" for n, e in e32.items()))
+    gates = {n: case_gate(e) for n, e in e32.items()}
+    print(f"[deform_conv2d backward] {CASES[i]}: gate        " + "  ".join(f"{n} {g:.2e}" for n, g in gates.items()))
+    return gates
+
+
+def check(tag, got, ref, names, gates=GATE):
     errs = {n: relerr(got[n], ref[n]) for n in names}
     print(f"[deform_conv2d backward] {tag}: " + "  ".join(f"{n} {e:.2e}" for n, e in errs.items()))
     for n, e in errs.items():
         assert got[n].shape == ref[n].shape and got[n].dtype == torch.float32
-        assert e <= GATE[n], (tag, n, e)
+        assert e <= gates[n], (tag, n, e, gates[n])
 
 
 @pytest.mark.parametrize("i", range(len(CASES)))
 def test_backward_matches_the_float64_oracle(dev, i):
     x, off, w, b, mask, R = make_case(i)
     ref = reference(i)
+    gates = case_gates(i)                                         # (before the operator runs: printed whatever happens next)
     got, _ = op_grads(dev, x, off, w, b, mask, R)
     if mask is None:
         assert got["gmask"] is None and ref["gmask"] is None
-    check(str(CASES[i]), got, ref, [n for n in NAMES if ref[n] is not None])
+    check(str(CASES[i]), got, ref, [n for n in NAMES if ref[n] is not None], gates)
 
 
 # ---- known answers ----
@@ -165,11 +203,12 @@ def test_only_the_kernels_needs_input_grad_asks_for_are_launched(dev, monkeypatc
 
 
 def test_weight_and_bias_gradients_are_bitwise_reproducible(dev):
-    x, off, w, b, mask, R = make_case(2)
-    g1, _ = op_grads(dev, x, off, w, b, mask, R)
-    g2, _ = op_grads(dev, x, off, w, b, mask, R)
-    assert torch.equal(g1["gw"], g2["gw"]) and torch.equal(g1["gbias"], g2["gbias"])
-    check("second call", g2, reference(2), ("gx",))               # (float atomics: compared under the gate only)
+    for i in (2, CASES.index((1, 512, 256, 35, 53, 2.0, True))):  # three slabs; seven capped ones, the last short
+        x, off, w, b, mask, R = make_case(i)
+        g1, _ = op_grads(dev, x, off, w, b, mask, R)
+        g2, _ = op_grads(dev, x, off, w, b, mask, R)
+        assert torch.equal(g1["gw"], g2["gw"]) and torch.equal(g1["gbias"], g2["gbias"]), CASES[i]
+        check(f"second call {CASES[i]}", g2, reference(i), ("gx",), case_gates(i))   # (float atomics: compared under the gate only)
 
 
 def test_the_reference_deformconv_call_sequence_trains(dev):

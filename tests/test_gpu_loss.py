@@ -22,7 +22,9 @@ values / over the gradients of a case):
     dense_unc_mask0    6.1e-08    1.2e-07
     dense_camera       1.4e-07    2.3e-07
     dense_early        1.1e-07    9.7e-08
-    worst              1.5e-07    2.3e-07
+    manyrows           1.2e-07    1.4e-07
+    bigmap             2.1e-07    1.2e-07
+    worst              2.1e-07    2.3e-07
 
 Every one is below 2.5e-6, so the gate is 5e-6 for every value and every gradient."""
 import functools
@@ -150,7 +152,7 @@ def test_known_answer_one_object_one_l1_head(dev):
     assert torch.equal(pred.grad.cpu(), g)
 
 
-@pytest.mark.parametrize("i", [0, 3, 5])
+@pytest.mark.parametrize("i", [0, 3, 5, loss_ref.NAMES.index("bigmap")])      # bigmap: the partial sums under the 1024-workgroup cap
 def test_repeated_calls_are_bit_identical(dev, i):
     outputs, batch, _ = loss_ref.clone_case(i, device=dev)
     crit = criterion(i)
@@ -158,6 +160,50 @@ def test_repeated_calls_are_bit_identical(dev, i):
         a = torch.stack(list(crit(outputs, batch)[1].values())).cpu()
         b = torch.stack(list(crit(outputs, batch)[1].values())).cpu()
     assert torch.equal(a, b)
+
+
+def test_unaligned_heat_maps_take_the_scalar_path(dev):
+    """`heat` and `heat_gt` as contiguous views that start one float into a larger buffer: 4-byte aligned, so the dense passes
+    vectorise nothing (nvec = 0, forward and backward) and the whole map goes through the scalar loops - the maps and objects of
+    case `dense`, every value and the heat map's gradient against that case's float64 restatement"""
+    from centerfusiondetect3d_amd import ops
+    i = loss_ref.NAMES.index("dense")
+    ref_v, ref_g = reference(i)
+    outputs, batch, _ = loss_ref.clone_case(i, device=dev)
+    out, weights = outputs[0], loss_ref.config_for(i).weights
+    shape = out["heatmap"].shape
+    assert tuple(shape) == (2, 10, 16, 24)
+    n, pad = out["heatmap"].numel(), 4
+
+    def off_by_one_float(t, leaf=False):
+        buf = torch.full((n + 2 * pad,), float("nan"), device=dev)  # (NaN around the map: a read outside it shows in the values)
+        buf[1:1 + n] = t.reshape(-1)
+        buf.requires_grad_(leaf)
+        view = buf[1:1 + n].view(shape)
+        assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 4 and view.is_contiguous()
+        return buf, view
+    hbuf, heat = off_by_one_float(out["heatmap"], leaf=True)
+    _, heat_gt = off_by_one_float(batch["heatmap0"])
+    table, names = [], []
+    for name in ("depth", "depth2"):
+        table.append((ops.LOSS_L1, out[name], batch["depth"], None, weights["depth"]))
+        names.append(name)
+    for name in loss_ref.L1_HEADS:
+        table.append((ops.LOSS_L1, out[name], batch[name], None, weights[name]))
+        names.append(name)
+    for name in ("rotation", "rotation2"):
+        table.append((ops.LOSS_BINROT, out[name], batch["rotres"], batch["rotbin"], weights[name]))
+        names.append(name)
+    table.append((ops.LOSS_BCE, out["nuscenes_att"], batch["nuscenes_att"], batch["nuscenes_att_mask"], weights["nuscenes_att"]))
+    names.append("nuscenes_att")
+    total, vec, _ = ops.generic_loss(heat, heat_gt, batch["target"]["heatCenters"], batch["widthHeight"], batch["mask"],
+                                     batch["classIds"], table, heat_weight=weights["heatmap"], out_area=shape[2] * shape[3])
+    slot = {"heatmap": 0, "total": len(names) + 1, **{name: 1 + j for j, name in enumerate(names)}}
+    assert set(slot) >= {k for k, r in ref_v.items() if r != 0}
+    check_values("scalar path", {k: vec[slot.get(k, len(names) + 2)] for k in ref_v}, ref_v)
+    assert float(total.detach()) == float(vec[slot["total"]])
+    total.backward()
+    check_grad("scalar path", "heatmap", hbuf.grad[1:1 + n].view(shape), ref_g["heatmap"])
 
 
 def test_upstream_gradient_scales_the_gradients(dev):
