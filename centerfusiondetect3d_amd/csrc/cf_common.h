@@ -113,3 +113,21 @@ static inline float cf_resolve_in_scale(float s) {
 }
 
 __device__ __forceinline__ float cf_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// [s, e) = what Python's a[start:stop] selects of n elements (the frustum and radar-expansion kernels clip their boxes with it)
+__device__ __forceinline__ void py_slice(int start, int stop, int n, int& s, int& e) {
+  if (start < 0) {
+    start += n;
+    if (start < 0) start = 0;
+  } else if (start > n) {
+    start = n;
+  }
+  if (stop < 0) {
+    stop += n;
+    if (stop < 0) stop = 0;
+  } else if (stop > n) {
+    stop = n;
+  }
+  s = start;
+  e = stop;
+}

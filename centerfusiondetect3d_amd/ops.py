@@ -1048,10 +1048,9 @@ def serialize_nuscenes(post, trans_matrix, velocity_matrix, cs_rot=None, pose_ro
     return rows, rotation, order, counts
 
 
-def pillar_expand(pc_2d, pc_3d, counts, calib, trans, out_hw, pillar_dims=(1.5, 0.2, 0.2),
-                  want_aux=False):
-    """pc_2d (B,3,Nmax) f64, pc_3d (B,R,Nmax) f64, counts (B) i32, calib (B,3,4) f64,
-    trans (B,2,3) f64  ->  pc_dep (B,3,H,W) f32 [, keep (B,Nmax) u8, xy (B,2,Nmax) f64]."""
+def _radar_expand(entry, extra, pc_2d, pc_3d, counts, calib, trans, out_hw, want_aux):
+    """What cf_pillar_expand and cf_radar_roi_expand share: the input checks, the outputs and the call (`extra`: the
+    arguments between W and pc_dep).  -> pc_dep (B,3,H,W) f32 [, keep (B,Nmax) u8, xy (B,2,Nmax) f64]."""
     _need_cuda(pc_2d, pc_3d, counts, calib, trans)
     B, _, max_n = pc_2d.shape
     H, W = out_hw
@@ -1062,14 +1061,19 @@ def pillar_expand(pc_2d, pc_3d, counts, calib, trans, out_hw, pillar_dims=(1.5, 
     for t, dt in ((pc_2d, torch.float64), (pc_3d, torch.float64), (counts, torch.int32),
                   (calib, torch.float64), (trans, torch.float64)):
         if t.dtype != dt or not t.is_contiguous():
-            raise _lib.CfHipError("cf_pillar_expand: wrong dtype / non-contiguous input")
-    h, w, l = pillar_dims
-    _lib.check(_lib.load().cf_pillar_expand(pc_2d.data_ptr(), pc_3d.data_ptr(), counts.data_ptr(),
-                                            B, max_n, pc_3d.shape[1], calib.data_ptr(),
-                                            trans.data_ptr(), H, W, float(h), float(w), float(l),
-                                            pc_dep.data_ptr(), _lib.ptr(keep), _lib.ptr(xy),
-                                            _lib.stream_ptr()), "cf_pillar_expand")
+            raise _lib.CfHipError(f"{entry}: wrong dtype / non-contiguous input")
+    _lib.check(getattr(_lib.load(), entry)(pc_2d.data_ptr(), pc_3d.data_ptr(), counts.data_ptr(), B, max_n, pc_3d.shape[1],
+                                           calib.data_ptr(), trans.data_ptr(), H, W, *extra, pc_dep.data_ptr(),
+                                           _lib.ptr(keep), _lib.ptr(xy), _lib.stream_ptr()), entry)
     return (pc_dep, keep, xy) if want_aux else pc_dep
+
+
+def pillar_expand(pc_2d, pc_3d, counts, calib, trans, out_hw, pillar_dims=(1.5, 0.2, 0.2),
+                  want_aux=False):
+    """pc_2d (B,3,Nmax) f64, pc_3d (B,R,Nmax) f64, counts (B) i32, calib (B,3,4) f64,
+    trans (B,2,3) f64  ->  pc_dep (B,3,H,W) f32 [, keep (B,Nmax) u8, xy (B,2,Nmax) f64]."""
+    return _radar_expand("cf_pillar_expand", [float(v) for v in pillar_dims], pc_2d, pc_3d, counts, calib, trans, out_hw,
+                         want_aux)
 
 
 ROI_METHODS = {"pillars": 0, "points": 1, "heatmap": 2}     # DATASET.PC_ROI_METHOD -> `method` of cf_radar_roi_expand
@@ -1088,22 +1092,7 @@ def radar_roi_expand(pc_2d, pc_3d, counts, calib, trans, out_hw, roi_method, wan
     method = roi_method_id(roi_method)
     if method == 0:
         raise ValueError("radar_roi_expand: 'pillars' is pillar_expand (it needs the pillar dimensions)")
-    _need_cuda(pc_2d, pc_3d, counts, calib, trans)
-    B, _, max_n = pc_2d.shape
-    H, W = out_hw
-    dev = pc_2d.device
-    pc_dep = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32)
-    keep = torch.empty((B, max_n), device=dev, dtype=torch.uint8) if want_aux else None
-    xy = torch.empty((B, 2, max_n), device=dev, dtype=torch.float64) if want_aux else None
-    for t, dt in ((pc_2d, torch.float64), (pc_3d, torch.float64), (counts, torch.int32),
-                  (calib, torch.float64), (trans, torch.float64)):
-        if t.dtype != dt or not t.is_contiguous():
-            raise _lib.CfHipError("cf_radar_roi_expand: wrong dtype / non-contiguous input")
-    _lib.check(_lib.load().cf_radar_roi_expand(pc_2d.data_ptr(), pc_3d.data_ptr(), counts.data_ptr(),
-                                               B, max_n, pc_3d.shape[1], calib.data_ptr(), trans.data_ptr(), H, W, method,
-                                               pc_dep.data_ptr(), _lib.ptr(keep), _lib.ptr(xy),
-                                               _lib.stream_ptr()), "cf_radar_roi_expand")
-    return (pc_dep, keep, xy) if want_aux else pc_dep
+    return _radar_expand("cf_radar_roi_expand", [method], pc_2d, pc_3d, counts, calib, trans, out_hw, want_aux)
 
 
 def stem_args(ps, x, out, shape=None, out_pool=None, in_scales=None, into=None) -> _lib.StemArgs:

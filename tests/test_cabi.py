@@ -98,6 +98,21 @@ def test_argument_validation_without_gpu():
     assert lib.cf_upsample_dw(None, None, None, None, 1, 1, 1, 4, 2, None) == -22
 
 
+def test_frustum_map_bound_without_gpu():
+    """The frustum kernel's ROI search divides by multiplication, exact while W * W * H < 2^32: both entry points refuse a
+    larger map before they look at a pointer (all-null calls: nothing here can reach a launch)."""
+    from centerfusiondetect3d_amd import _lib
+    lib = _lib.load()
+    assoc = lambda H, W: lib.cf_frustum_assoc(None, 100, None, None, None, None, None, None, 1, H, W, 60.0, None, None, None, None)
+    chain = lambda H, W: lib.cf_topk_frustum(None, 10, 100, None, None, None, None, None, None, 1, H, W, 60.0, None, None, None,
+                                             None, None, None, None, None)
+    for call, name in ((assoc, b"cf_frustum_assoc"), (chain, b"cf_topk_frustum")):
+        assert call(2048, 2048) == -22
+        assert name in lib.cf_last_error() and b"W * W * H must stay below 2^32" in lib.cf_last_error()
+        assert call(112, 200) == -22
+        assert name in lib.cf_last_error() and b"null buffer" in lib.cf_last_error()
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from centerfusiondetect3d_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)

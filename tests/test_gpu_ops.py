@@ -350,6 +350,41 @@ def test_topk_and_guard_at_large_k(dev):
     assert np.array_equal(a.cpu().numpy(), frustum_ref.pc_frustum_heatmap(y, pc_dep, calib, 160, 60.0).numpy())
 
 
+def _guard_maps():
+    g = torch.Generator().manual_seed(33)
+    flat = torch.full((2, 10, 112, 200), 1e-4)
+    # (name, map, K, the element that changes between the two checksums, its new value)
+    return [("all ties", flat, 100, (1, 9, 111, 199), 0.0),                  # every slice takes the tie-selection path
+            ("plateau + ties", cases.decode_case(3, tie_heavy=True)["heatmap"], 100, (0, 4, 50, 60), 2.0),
+            ("short odd slices", torch.rand(3, 2, 17, 23, generator=g), 7, (2, 1, 16, 22), 2.0),   # 49 elements per slice
+            ("tiny slices", torch.rand(1, 1, 5, 40, generator=g), 100, (0, 0, 2, 20), 2.0)]        # 13 <= K per slice, C*H*W = 200 >= K
+
+
+@pytest.mark.parametrize("case", range(4))
+def test_topk_guard_fallback_on_tie_and_tiny_slice_paths(dev, case):
+    """The guard's fallback (`topk_fallback_kernel`: the 256-thread slice body sixteen times in ONE workgroup over the same LDS,
+    then the merge) where the slice body leaves its main path: tie selection, slices shorter than the workgroup, slices of at
+    most K elements.  One element changes between the two checksums, so the fallback runs; bit for bit = cf_topk_peaks behind
+    the NMS = the oracle's top-K of the suppressed map."""
+    from centerfusiondetect3d_amd import ops
+    _, heat, K, at, value = _guard_maps()[case]
+    hd = heat.to(dev)
+    P = ops.CHECKSUM_PARTS
+    sums = torch.empty(2 * P, device=dev, dtype=torch.int64)
+    ops.checksum64(hd, out=sums[:P])
+    assert float(hd[at]) != value
+    hd[at] = value
+    ops.checksum64(hd, out=sums[P:])
+    assert not torch.equal(sums[:P], sums[P:])
+    plain = ops.topk_peaks(hd, K, nms=True)
+    carried = tuple(torch.full_like(t, 7) for t in plain)
+    out = ops.topk_peaks(hd, K, nms=True, out=carried, only_if_changed=sums)
+    ref = frustum_ref.topk(decode_ref.nms(hd.cpu()), K)[:3]
+    for got, same, want in zip(out, plain, ref):
+        assert torch.equal(got, same)
+        assert np.array_equal(got.cpu().numpy(), want.numpy())
+
+
 def test_frustum_no_radar_and_single_box(dev):
     from centerfusiondetect3d_amd import ops
     y, pc_dep, calib = cases.frustum_case(5, B=1)

@@ -15,7 +15,7 @@ import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "centerfusiondetect3d_amd", "csrc")
 SOURCES = {"cf_conv3x3_f16.hip": ("conv3x3_f16x3_kernel",), "cf_heads.hip": ("head_patch16_kernel",),
-           "cf_gemm_f16.hip": ("dcn_f16x3_kernel", "conv_f16x3_kernel"), "cf_post.hip": ("pc_hm_direct_kernel",),
+           "cf_gemm_f16.hip": ("dcn_f16x3_kernel", "conv_f16x3_kernel"), "cf_frustum.hip": ("pc_hm_direct_kernel",),
            "cf_stem_early.hip": ("stem_early_kernel",),
            "cf_dcn_bwd.hip": ("dcn_bwd_data_kernel", "dcn_bwd_weight_kernel")}
 
