@@ -127,6 +127,18 @@ class LossArgs(C.Structure):
                 ("workspace", _f), ("workspace_bytes", C.c_size_t), ("grad_out", _f), ("gheat", _f)]
 
 
+CF_HEAD_TRAIN_MAX_HIDDEN = 2
+_HT_LAYERS = CF_HEAD_TRAIN_MAX_HIDDEN + 2
+
+
+class HeadTrainArgs(C.Structure):
+    _fields_ = [("x", _f), ("x2", _f), ("x_stride", C.c_int32), ("c_x", C.c_int32), ("x2_stride", C.c_int32),
+                ("c_x2", C.c_int32), ("B", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("n_hidden", C.c_int32),
+                ("hidden", C.c_int32), ("n_out", C.c_int32), ("chunk_px", C.c_int32),
+                ("weight", _f * _HT_LAYERS), ("bias", _f * _HT_LAYERS), ("y", _f), ("gy", _f),
+                ("gw", _f * _HT_LAYERS), ("gb", _f * _HT_LAYERS), ("workspace", _f), ("workspace_bytes", C.c_size_t)]
+
+
 # every symbol include/cf_hip.h declares: (restype, argtypes)
 _i, _d = C.c_int, C.c_double
 SYMBOLS = {
@@ -155,6 +167,11 @@ SYMBOLS = {
     "cf_loss_forward": (_i, [C.POINTER(LossArgs), _f]),
     "cf_loss_backward": (_i, [C.POINTER(LossArgs), _f]),
     "cf_loss_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "cf_head_train_forward": (_i, [C.POINTER(HeadTrainArgs), _f]),
+    "cf_head_backward": (_i, [C.POINTER(HeadTrainArgs), _f]),
+    "cf_head_train_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "cf_head_bwd_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "cf_head_bwd_chunk_px": (_i, [_i, _i, _i, _i]),
     "cf_upsample_dw": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _f]),
     "cf_maxpool2x2": (_i, [_f, _f, _i, _i, _i, _i, _f]),
     "cf_nchw_to_nhwc4": (_i, [_f, _f, _i, _i, _i, _i, _f]),

@@ -29,6 +29,7 @@ SOURCES = [
     ("cf_stem.hip", []),
     ("cf_stem_early.hip", []),
     ("cf_heads.hip", []),
+    ("cf_heads_bwd.hip", []),
     ("cf_elementwise.hip", []),
     ("cf_topk.hip", ["-ffp-contract=off"]),
     ("cf_frustum.hip", ["-ffp-contract=off"]),

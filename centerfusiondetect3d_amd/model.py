@@ -5,7 +5,7 @@ Drop-in boundary: same factory (`getModel(config)`, model/mod
 base_model.py:30-53 + detectHeads.py:32-163), same call
 `model(images, pc_hm=None, pc_dep=None, calib=None) -> [dict]` (base_model.py:67-106) with the
 same keys, order, shapes and the `pc_hm_in` view of the caller's `pc_dep`
-(detectHeads.py:172).  Eval mode only - training is outside the hot path.
+(detectHeads.py:172).  Eval mode, and one training mode: the heads on a frozen trunk (MODEL.FREEZE_BACKBONE, `_forward_train`).
 
 Nothing else is shared with the reference's design.  The module is a parameter tree plus an
 *execution plan*: at first call for a given (B,H,W) it lays out every intermediate NHWC buffer in
@@ -246,7 +246,28 @@ class DLASeg(nn.Module):
         self.range_headroom = 8.0  # a calibrated layer keeps max |input| * scale <= 65504 / this
         self._range_checked = False  # a check_ranges / calibrate has run on these weights (Detector's first-batch guard)
         self.register_load_state_dict_post_hook(lambda m, _k: m._weights_changed())
+        # MODEL.FREEZE_BACKBONE (dla.py:617-621): base, dla_up and ida_up stay frozen, the detection heads learn - the one training
+        # mode of this model (_forward_train).  Without it every parameter stays an inference constant, as before.
+        self.freezeBackbone = bool(getattr(config.MODEL, "FREEZE_BACKBONE", False))
+        if self.freezeBackbone:
+            for name, p in self.named_parameters():
+                p.requires_grad_(name.startswith("detectHead_0."))
+        self._stale = False      # a training forward has run: the packed head weights may lag an optimiser step (eval re-packs)
         self.eval()
+
+    def train(self, mode=True):
+        super().train(mode)
+        if not mode:
+            self._repack_if_stale()
+        return self
+
+    def _repack_if_stale(self):
+        """Behind a training forward the eval path's packed head weights may be an optimiser step old: drop them (and the plans
+        built on them).  The trunk did not change, so the calibrated ranges stay."""
+        if getattr(self, "_stale", False):
+            with self._lock:
+                self._stale = False
+                self.invalidate()
 
     def _weights_changed(self):
         """load_state_dict: new weights - re-pack lazily, and whatever was known about the activation ranges is void."""
@@ -621,7 +642,11 @@ class DLASeg(nn.Module):
     # ----------------------------------------------------------------------------------- forward
     def forward(self, x, pc_hm=None, pc_dep=None, calib=None):
         if self.training:
-            raise NotImplementedError("training is outside the hot path; call model.eval()")
+            if not self.freezeBackbone:
+                raise NotImplementedError("training: only the frozen-backbone mode is implemented (build the model with "
+                                          "MODEL.FREEZE_BACKBONE = True: the heads learn on the frozen trunk); call model.eval()")
+            return self._forward_train(x, pc_hm, pc_dep, calib)
+        self._repack_if_stale()
         if not x.is_cuda:
             raise _lib.CfHipError("DLASeg.forward needs device tensors: the HIP path has no CPU fallback")
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
@@ -649,6 +674,122 @@ class DLASeg(nn.Module):
             if self.use_graph:
                 return self._forward_graph(x, pc_dep, calib, B, H, W, dev, sid)
             return self._forward_eager(x, pc_dep, calib, B, H, W, dev, sid)
+
+    # ---------------------------------------------------------------------------------- training
+    def _head_params(self, h):
+        """(weights, biases) of head h: the module's own nn.Parameters in layer order (indices 0, 2, 4, ... of the Sequential)"""
+        n = len(self.config.head_conv[h]) + 1
+        return ([self.get_parameter(f"detectHead_0.{h}.{2 * i}.weight") for i in range(n)],
+                [self.get_parameter(f"detectHead_0.{h}.{2 * i}.bias") for i in range(n)])
+
+    def _train_trunk(self, x, pc, B, H, W, dev, sid):
+        """The frozen trunk of a training forward: the eval plan's launches (split-fp16, BN folded with the running statistics)
+        under no_grad -> the (B, H/4, W/4, 64) NHWC feature map, a buffer of the plan (valid until the next training forward of
+        this shape on this stream).  model.streams > 1: sub-batches on concurrent streams, under the eval forward's rule.
+        pc (early fusion): the normalised radar map the stem reads."""
+        h4, w4, n = H // 4, W // 4, int(self.streams)
+        if not (n > 1 and B % n == 0 and (B // n) * H * W >= self.min_sub_batch * 448 * 800):
+            n = 1
+        k = B // n
+
+        def first():
+            feat = torch.empty((B, h4, w4, 64), device=dev, dtype=torch.float32)
+            p = _Plan(self, k, H, W, dev, part="trunk", feat=feat[:k])
+            p.train_feat = feat
+            return p
+
+        with torch.no_grad():
+            p0 = self._plan((B, H, W, dev, sid, "train-trunk", 0, n), first)
+            feat = p0.train_feat
+            if n == 1:
+                p0.run_trunk(x, pc)
+                return feat
+            cur = torch.cuda.current_stream(dev)
+            pool = _side_streams(dev, sid, n)
+            for i in range(n):
+                sl = slice(i * k, (i + 1) * k)
+                tp = p0 if i == 0 else self._plan((B, H, W, dev, sid, "train-trunk", i, n),
+                                                  lambda: _Plan(self, k, H, W, dev, part="trunk", feat=feat[sl]))
+                s = cur if i == n - 1 else pool[i]
+                if s is not cur:
+                    s.wait_stream(cur)
+                with torch.cuda.stream(s):
+                    tp.run_trunk(x[sl], pc[sl] if pc is not None else None)
+            for s in pool[:n - 1]:
+                cur.wait_stream(s)
+            return feat
+
+    def _forward_train(self, x, pc_hm, pc_dep, calib):
+        """model.train() with MODEL.FREEZE_BACKBONE: the reference's training forward (base_model.py:83-106, detectHeads.py:117-191)
+        with the trunk frozen.  The trunk runs through the eval plan under no_grad; every head runs through `ops.head_stack` on the
+        module's own parameters, so `loss.backward()` leaves a gradient on each `detectHead_0.*` parameter and on nothing else.
+        Middle fusion: the caller's `pc_hm` (B,3,H/4,W/4) - the dataset's association map - feeds the secondary heads; no frustum
+        association runs and nothing is normalised in place.  Early fusion: `pc_hm` is the map the six-channel stem reads.
+        Deviation from the reference: the frozen trunk always uses the folded running statistics of its BatchNorm layers (the
+        reference leaves dla_up / ida_up - and, without MODEL.NORM_EVAL, base - in batch-statistics mode)."""
+        if self.use_graph:
+            raise NotImplementedError("training mode: model.use_graph is not supported (autograd does not record through a captured "
+                                      "graph); set model.use_graph = False")
+        if not x.is_cuda:
+            raise _lib.CfHipError("DLASeg.forward needs device tensors: the HIP path has no CPU fallback")
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
+            raise ValueError(f"images must be (B,3,H,W) with H,W multiples of 32, got {tuple(x.shape)}")
+        B, _, H, W = x.shape
+        dev = x.device
+        h4, w4 = H // 4, W // 4
+        x = x.detach().float().contiguous()
+        middle = self.isRadarEnabled and not self.isEarly
+        if self.isRadarEnabled:
+            if pc_hm is None:
+                raise ValueError("radar model in training mode: pc_hm (the dataset's radar map) is required - no frustum "
+                                 "association runs in training (detectHeads.py:176-181)")
+            if tuple(pc_hm.shape) != (B, 3, h4, w4) or pc_hm.dtype != torch.float32:
+                raise ValueError(f"pc_hm must be float32 {(B, 3, h4, w4)}, got {pc_hm.dtype} {tuple(pc_hm.shape)}")
+            if middle and (pc_dep is None or tuple(pc_dep.shape) != (B, 3, h4, w4)):
+                raise ValueError(f"radar model: pc_dep must be {(B, 3, h4, w4)}")
+            pc_hm = pc_hm.detach().contiguous()
+        heads, secondary = self.config.heads, (SECONDARY_HEADS if middle else [])
+        with self._lock, torch.cuda.device(dev):
+            if self._packed is None:
+                self._prepare(dev)
+            sid = torch.cuda.current_stream(dev).cuda_stream
+            # (a copy: autograd keeps the map until backward, the plan's buffer is overwritten by the next forward)
+            feat = self._train_trunk(x, pc_hm if self.isEarly else None, B, H, W, dev, sid).clone()
+            self._stale = True
+            y = {}
+
+            def run(h, x2n):
+                ws, bs = self._head_params(h)
+                final = "heatmap" if h == "heatmap" else ("depth" if h in ("depth", "depth2") else None)
+                return ops.head_stack_nhwc(feat, 64, x2n, 0 if x2n is None else 3, ws, bs, final=final)
+
+            for h in heads:
+                if h in secondary:
+                    continue
+                r = run(h, None)
+                y[h] = r[0] if isinstance(r, tuple) else r
+                if h == "depth":
+                    depth_raw = r[1]
+            if "depth" in heads:
+                y["depthMap"] = depth_raw
+            y["calib"] = calib
+            if middle:
+                y["pc_hm_in"] = pc_dep[:, :1]
+                y["pc_hm"] = pc_hm[:, 0, :, :].unsqueeze(1)
+                with torch.no_grad():
+                    pcn = ops.nchw_to_nhwc(pc_hm)
+                for h in secondary:
+                    if h not in heads:
+                        continue
+                    r = run(h, pcn)
+                    y[h] = r[1] if h == "depth2" else r          # (depth2: the raw map until depthMap has taken it)
+                    if h == "depth2":
+                        act = r[0]
+                y["pc_hm_out"] = pc_hm[:, :1]
+                if "depth2" in heads:
+                    y["depthMap"] = y["depth2"]
+                    y["depth2"] = act
+        return [y]
 
     def _forward_eager(self, x, pc_dep, calib, B, H, W, dev, sid, store=None):
         # (min_sub_batch counts 448 x 800 frames: a sub-batch of a larger input carries proportionally more work)

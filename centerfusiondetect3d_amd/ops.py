@@ -599,8 +599,8 @@ def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0
     fixed order and cannot.  At an integer sampling position the offset gradient is the right-hand derivative, as
     torchvision's is.  The range check and the packed-weight cache behave as in inference: an optimizer's in-place step
     bumps the weight's version, so the next forward packs it again.  Otherwise (no_grad, nothing requiring grad) the
-    inference path runs as it always did and the result carries no grad_fn.  The module path (`DLASeg`) stays
-    eval-only."""
+    inference path runs as it always did and the result carries no grad_fn.  The module path (`DLASeg`) never
+    differentiates its trunk (it trains its heads only: `head_stack`)."""
     _need_cuda(input, offset, weight, bias, mask)
     if input.dim() != 4 or weight.dim() != 4:
         raise ValueError("deform_conv2d: input must be (B,Cin,H,W) and weight (Cout,Cin,kh,kw)")
@@ -784,6 +784,156 @@ def generic_loss(heat, heat_gt, centers, wh, mask, cls, heads, heat_weight=1.0, 
         return _GenericLossFn.apply(spec, *tensors)
     with torch.no_grad():
         return _loss_run_forward(spec, tensors)[:3]
+
+
+# ---- one detection head under autograd (cf_head_train_forward / cf_head_backward) ----
+HEAD_HIDDEN = 256          # width of every hidden map the training kernels implement
+HEAD_MAX_OUT = 16          # outputs of a head's last layer
+HEAD_MAX_HIDDEN = _lib.CF_HEAD_TRAIN_MAX_HIDDEN   # 1x1 hidden layers behind the 3x3
+HEAD_FINALS = (None, "heatmap", "depth")
+
+
+def _head_check(x, x2, weights, biases, final):
+    """Shapes / dtypes of a head_stack call (no device needed) -> (Cin of x, Cin of x2, n_hidden, n_out)."""
+    if final not in HEAD_FINALS:
+        raise ValueError(f"head_stack: final must be one of {HEAD_FINALS}, got {final!r}")
+    weights, biases = list(weights), list(biases)
+    if len(weights) != len(biases) or not 2 <= len(weights) <= HEAD_MAX_HIDDEN + 2:
+        raise NotImplementedError(f"head_stack: a 3x3 layer, 0..{HEAD_MAX_HIDDEN} hidden 1x1 layers and an output layer "
+                                  f"(2..{HEAD_MAX_HIDDEN + 2} weights with their biases), got {len(weights)} / {len(biases)}")
+    for t in (x, x2, *weights, *biases):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
+            raise NotImplementedError("head_stack: float32 tensors only (no autocast, no fp16 / bf16 / float64)")
+    if x.dim() != 4 or (x2 is not None and (x2.dim() != 4 or x2.shape[0] != x.shape[0] or x2.shape[2:] != x.shape[2:])):
+        raise ValueError("head_stack: x must be (B,Cin,h,w) and the second source (B,C2,h,w) on the same map")
+    c_x, c_x2 = x.shape[1], (0 if x2 is None else x2.shape[1])
+    cin = c_x + c_x2
+    if cin > 512:
+        raise NotImplementedError(f"head_stack: Cin={cin} above the limit of 512")
+    if tuple(weights[0].shape) != (HEAD_HIDDEN, cin, 3, 3):
+        raise NotImplementedError(f"head_stack: the first layer must be a 3x3 convolution ({HEAD_HIDDEN},{cin},3,3) - hidden width "
+                                  f"{HEAD_HIDDEN} only - got {tuple(weights[0].shape)}")
+    for w in weights[1:-1]:
+        if tuple(w.shape) != (HEAD_HIDDEN, HEAD_HIDDEN, 1, 1):
+            raise NotImplementedError(f"head_stack: hidden layers must be 1x1 convolutions ({HEAD_HIDDEN},{HEAD_HIDDEN},1,1), "
+                                      f"got {tuple(w.shape)}")
+    n_out = weights[-1].shape[0]
+    if weights[-1].dim() != 4 or tuple(weights[-1].shape[1:]) != (HEAD_HIDDEN, 1, 1) or not 1 <= n_out <= HEAD_MAX_OUT:
+        raise NotImplementedError(f"head_stack: the output layer must be a 1x1 convolution (Cout,{HEAD_HIDDEN},1,1) with "
+                                  f"1 <= Cout <= {HEAD_MAX_OUT}, got {tuple(weights[-1].shape)}")
+    for w, b in zip(weights, biases):
+        if tuple(b.shape) != (w.shape[0],):
+            raise ValueError(f"head_stack: bias {tuple(b.shape)} does not fit weight {tuple(w.shape)}")
+    return c_x, c_x2, len(weights) - 2, n_out
+
+
+def head_train_args(xn, c_x, x2n, c_x2, weights, biases, chunk_px=0) -> _lib.HeadTrainArgs:
+    """The argument block of cf_head_train_forward / cf_head_backward without outputs and workspace.  xn (B,h,w,S >= c_x) and
+    x2n (B,h,w,S2 >= c_x2) or None: contiguous fp32 NHWC; weights / biases: contiguous fp32 in layer order."""
+    a = _lib.HeadTrainArgs()
+    a.B, a.h, a.w = xn.shape[:3]
+    a.x, a.x_stride, a.c_x = xn.data_ptr(), xn.shape[-1], c_x
+    if x2n is not None:
+        a.x2, a.x2_stride, a.c_x2 = x2n.data_ptr(), x2n.shape[-1], c_x2
+    a.n_hidden, a.hidden, a.n_out, a.chunk_px = len(weights) - 2, HEAD_HIDDEN, weights[-1].shape[0], int(chunk_px)
+    for l, (w, b) in enumerate(zip(weights, biases)):
+        a.weight[l], a.bias[l] = w.data_ptr(), b.data_ptr()
+    return a
+
+
+def _workspace(a, nbytes):
+    ws = torch.empty(nbytes, device=torch.device("cuda", torch.cuda.current_device()), dtype=torch.uint8)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    return ws
+
+
+class _HeadStackFn(torch.autograd.Function):
+    """`head_stack` under autograd: cf_head_train_forward; the NHWC sources and the raw weights saved (no hidden map is);
+    backward on cf_head_backward: every layer's weight and bias gradient, none for the sources."""
+
+    @staticmethod
+    def forward(ctx, xn, x2n, c_x, c_x2, chunk_px, n_layers, *params):
+        weights = [p.detach().contiguous() for p in params[:n_layers]]
+        biases = [p.detach().contiguous() for p in params[n_layers:]]
+        B, h, w = xn.shape[:3]
+        with torch.cuda.device(xn.device):
+            a = head_train_args(xn, c_x, x2n, c_x2, weights, biases, chunk_px)
+            y = torch.empty((B, a.n_out, h, w), device=xn.device, dtype=torch.float32)
+            a.y = y.data_ptr()
+            ws = _workspace(a, _lib.load().cf_head_train_workspace_bytes(B, h, w, c_x + c_x2, a.n_hidden, int(chunk_px)))
+            _lib.check(_lib.load().cf_head_train_forward(C.byref(a), _lib.stream_ptr()), "cf_head_train_forward")
+        ctx.meta = (c_x, c_x2, int(chunk_px), n_layers, x2n is not None)
+        ctx.save_for_backward(xn, *([x2n] if x2n is not None else []), *weights, *biases)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        c_x, c_x2, chunk_px, n, has2 = ctx.meta
+        saved = list(ctx.saved_tensors)
+        xn = saved.pop(0)
+        x2n = saved.pop(0) if has2 else None
+        weights, biases = saved[:n], saved[n:]
+        B, h, w = xn.shape[:3]
+        gy = gy.detach().to(torch.float32).contiguous()
+        with torch.cuda.device(xn.device):
+            a = head_train_args(xn, c_x, x2n, c_x2, weights, biases, chunk_px)
+            gws = [torch.empty_like(t) for t in weights]
+            gbs = [torch.empty_like(t) for t in biases]
+            for l in range(n):
+                a.gw[l], a.gb[l] = gws[l].data_ptr(), gbs[l].data_ptr()
+            a.gy = gy.data_ptr()
+            ws = _workspace(a, _lib.load().cf_head_bwd_workspace_bytes(B, h, w, c_x + c_x2, a.n_hidden, chunk_px))
+            _lib.check(_lib.load().cf_head_backward(C.byref(a), _lib.stream_ptr()), "cf_head_backward")
+        need = ctx.needs_input_grad[6:]
+        grads = [g if nd else None for g, nd in zip(gws + gbs, need)]
+        return (None, None, None, None, None, None, *grads)
+
+
+def head_final(y, final):
+    """The reference's output activation on a head's raw map: "heatmap" = clamp(sigmoid(y), 1e-4, 1 - 1e-4) (detectHeads.py:21-23;
+    zero gradient where the clamp binds), "depth" = 1 / (sigmoid(y) + 1e-6) - 1 (model/utils.py:141).  Elementwise torch ops."""
+    if final == "heatmap":
+        return torch.clamp(torch.sigmoid(y), min=1e-4, max=1 - 1e-4)
+    if final == "depth":
+        return 1.0 / (torch.sigmoid(y) + 1e-6) - 1.0
+    return y
+
+
+def head_stack_nhwc(xn, c_x, x2n, c_x2, weights, biases, final=None, chunk_px=0):
+    """`head_stack` on sources that are already NHWC: xn (B,h,w,S) whose first c_x channels are read, x2n (B,h,w,S2) / c_x2 the
+    optional second source (DLASeg's training forward: the trunk's feature map and the radar map, never concatenated)."""
+    weights, biases = list(weights), list(biases)
+    y = _HeadStackFn.apply(xn, x2n, int(c_x), int(c_x2), int(chunk_px), len(weights), *weights, *biases)
+    return y if final is None else (head_final(y, final), y)
+
+
+def head_stack(x, weights, biases, final=None, x2=None, chunk_px=0):
+    """One detection head of the reference (detectHeads.py:59-98) under autograd, on HIP kernels in both directions:
+    conv3x3(Cin -> 256) + bias -> ReLU -> [conv1x1(256 -> 256) + bias -> ReLU] x n -> conv1x1(256 -> Cout) + bias, n = 0 .. 2,
+    Cout = 1 .. 16.  `x` (B,Cin,h,w) fp32 on the device; `x2` (B,C2,h,w): an optional second source whose channels follow x's
+    (the 3 radar channels of the secondary heads - nothing is concatenated); `weights` / `biases`: the head's raw parameters in
+    layer order ((256,Cin+C2,3,3), (256,256,1,1) x n, (Cout,256,1,1)).  -> the raw map (B,Cout,h,w) when `final` is None;
+    (activated map, raw map) for final = "heatmap" / "depth" (`head_final`: torch elementwise ops on top of the operator).
+
+    Differentiable once in every weight and bias; NOT in x / x2 (a frozen trunk never asks; a source that requires grad raises
+    NotImplementedError).  The forward keeps no hidden map: the backward compacts the pixels with a non-zero output gradient on
+    the device and recomputes the hidden maps for those alone, with the forward's own kernel - its cost follows the number of
+    active pixels (plus one pass over dY and an empty launch per list chunk).  The forward is bitwise reproducible; the
+    gradients are summed with float atomics and can differ in their last bits from run to run.  `chunk_px`: list positions per
+    workspace chunk (a multiple of 64; 0 = 32768).  CPU tensors raise CfHipError, non-fp32 tensors and unsupported widths
+    NotImplementedError."""
+    weights, biases = list(weights), list(biases)
+    c_x, c_x2, _, _ = _head_check(x, x2, weights, biases, final)
+    _need_cuda(x, x2, *weights, *biases)
+    if torch.is_grad_enabled() and (x.requires_grad or (x2 is not None and x2.requires_grad)):
+        raise NotImplementedError("head_stack: the gradient with respect to x is not implemented (frozen trunk only): detach it")
+    if int(chunk_px) < 0 or int(chunk_px) % 64:
+        raise ValueError("head_stack: chunk_px must be a multiple of 64 (0: the default)")
+    with torch.no_grad(), torch.cuda.device(x.device):
+        xn = nchw_to_nhwc(x.contiguous())
+        x2n = None if x2 is None else nchw_to_nhwc(x2.contiguous())
+    return head_stack_nhwc(xn, c_x, x2n, c_x2, weights, biases, final, chunk_px)
 
 
 def upsample_dw(x, weight_kkc, f, skip=None, out=None):

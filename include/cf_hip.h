@@ -677,6 +677,45 @@ int cf_loss_forward(const cf_loss_args* a, void* stream);
 int cf_loss_backward(const cf_loss_args* a, void* stream);
 size_t cf_loss_workspace_bytes(int B, int C, int h, int w);
 
+/* Training path of ONE detection head on a frozen trunk (csrc/cf_heads_bwd.hip; added under ABI 7; replaces torch autograd over
+ * the nn.Sequential of detectHeads.py:59-98): conv3x3(Cin -> 256) + bias -> ReLU -> [conv1x1(256 -> 256) + bias -> ReLU] x
+ * n_hidden -> conv1x1(256 -> n_out) + bias, from the RAW fp32 weights, exact fp32-input MFMA products, fp32 accumulation.
+ * Cin = c_x + c_x2: the channels of `x` followed by those of the optional second source `x2` (the radar channels of the secondary
+ * heads: the concatenation is never materialised).  The hidden maps are not kept: both directions work through a list of pixels in
+ * chunks of `chunk_px` rows held in the workspace, and the backward recomputes the hidden maps with the forward's own kernel (its
+ * ReLU mask is the forward's bit for bit; ReLU'(0) = 0).  The gradient with respect to x is NOT produced. */
+#define CF_HEAD_TRAIN_MAX_HIDDEN 2
+typedef struct cf_head_train_args {
+  const float* x;        /* NHWC [B][h][w][x_stride], channels 0 .. c_x-1 read                                     */
+  const float* x2;       /* NHWC [B][h][w][x2_stride], channels 0 .. c_x2-1 read; NULL with c_x2 = 0               */
+  int32_t x_stride, c_x, x2_stride, c_x2;
+  int32_t B, h, w;
+  int32_t n_hidden;      /* 1x1 hidden layers, 0 .. CF_HEAD_TRAIN_MAX_HIDDEN                                       */
+  int32_t hidden;        /* width of every hidden map: 256                                                         */
+  int32_t n_out;         /* 1 .. 16                                                                                */
+  int32_t chunk_px;      /* list positions per chunk, a multiple of 64; 0 = the default (32768), capped by B*h*w   */
+  const float* weight[CF_HEAD_TRAIN_MAX_HIDDEN + 2]; /* raw torch layouts in layer order: [256][Cin][3][3], [256][256].., [n_out][256] */
+  const float* bias[CF_HEAD_TRAIN_MAX_HIDDEN + 2];
+  float* y;              /* forward out: NCHW [B][n_out][h][w], every element written                              */
+  const float* gy;       /* backward in: NCHW [B][n_out][h][w], arbitrary                                          */
+  float* gw[CF_HEAD_TRAIN_MAX_HIDDEN + 2];      /* backward out, in w's layouts; zeroed by the call                */
+  float* gb[CF_HEAD_TRAIN_MAX_HIDDEN + 2];
+  void* workspace;       /* 16-byte aligned; cf_head_train_workspace_bytes / cf_head_bwd_workspace_bytes           */
+  size_t workspace_bytes;
+} cf_head_train_args;
+/* 2 + n_hidden launches per chunk of the B*h*w pixels behind one weight re-layout per layer; bitwise reproducible. */
+int cf_head_train_forward(const cf_head_train_args* a, void* stream);
+/* A first pass compacts the pixels where any channel of gy is non-zero (a NaN counts) into a device-side list + count; the
+ * recompute, the chain and the weight-gradient launches then run per chunk of that list - grids come from the shapes, the work
+ * loops read the count, the host never waits; chunks behind the end of the list cost an empty launch each.  An all-zero gy gives
+ * exact zeros.  gw / gb are summed with float atomics and the list order comes from an atomic counter: the last bits can differ
+ * from run to run. */
+int cf_head_backward(const cf_head_train_args* a, void* stream);
+size_t cf_head_train_workspace_bytes(int B, int h, int w, int Cin, int n_hidden, int chunk_px);
+size_t cf_head_bwd_workspace_bytes(int B, int h, int w, int Cin, int n_hidden, int chunk_px);
+/* the chunk length those calls use for this geometry and chunk_px (0: the default) */
+int cf_head_bwd_chunk_px(int B, int h, int w, int chunk_px);
+
 /* Weight packing runs once per load_state_dict (BatchNorm fold, slot tables, split hi / lo planes, MFMA fragment order).
  * For the f16x3 convolution and DCN operators it is part of this ABI (cf_pack_conv_f16x3, cf_pack_dcn_f16 above: host-side C,
  * byte-identical to the Python packers); the heads', the stem's and the upsample's weights are packed by
