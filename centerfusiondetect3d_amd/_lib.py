@@ -139,6 +139,24 @@ class HeadTrainArgs(C.Structure):
                 ("gw", _f * _HT_LAYERS), ("gb", _f * _HT_LAYERS), ("workspace", _f), ("workspace_bytes", C.c_size_t)]
 
 
+CF_TARGETS_MAX_OBJS = 128
+CF_TARGETS_F = 20
+TGT_HAS_AMODAL, TGT_HAS_ATTRIBUTES, TGT_HAS_VELOCITY, TGT_HAS_ALPHA = 1, 2, 4, 8
+TGT_HAS_DEPTH, TGT_HAS_DIMENSION, TGT_HAS_LOCATION, TGT_HAS_YAW = 16, 32, 64, 128
+TGT_REP3D, TGT_NORM2D, TGT_WRITE_DEPTH, TGT_WRITE_ROT, TGT_FRUSTUM = 1, 2, 4, 8, 16
+
+
+class TargetsArgs(C.Structure):
+    _fields_ = [("ann", _f), ("iann", _f), ("counts", _f), ("trans", _f), ("calib", _f), ("scale", _f), ("pc_dep", _f),
+                ("B", C.c_int32), ("M", C.c_int32), ("C", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("flags", C.c_int32), ("max_pc_dist", C.c_float),
+                ("heat", _f), ("cls", _f), ("mask", _f), ("trunc_mask", _f), ("wh", _f), ("reg", _f), ("amodal_offset", _f),
+                ("dimension", _f), ("depth", _f), ("rotbin", _f), ("rotres", _f), ("att", _f), ("att_mask", _f),
+                ("velocity", _f), ("pc_hm", _f), ("t_bboxes", _f), ("t_scores", _f), ("t_centers", _f),
+                ("t_heat_centers", _f), ("t_bboxes3d", _f), ("t_rotation", _f), ("t_att", _f), ("t_velocity", _f),
+                ("workspace", _f), ("workspace_bytes", C.c_size_t)]
+
+
 # every symbol include/cf_hip.h declares: (restype, argtypes)
 _i, _d = C.c_int, C.c_double
 SYMBOLS = {
@@ -167,6 +185,8 @@ SYMBOLS = {
     "cf_loss_forward": (_i, [C.POINTER(LossArgs), _f]),
     "cf_loss_backward": (_i, [C.POINTER(LossArgs), _f]),
     "cf_loss_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "cf_targets_build": (_i, [C.POINTER(TargetsArgs), _f]),
+    "cf_targets_workspace_bytes": (C.c_size_t, [_i, _i]),
     "cf_head_train_forward": (_i, [C.POINTER(HeadTrainArgs), _f]),
     "cf_head_backward": (_i, [C.POINTER(HeadTrainArgs), _f]),
     "cf_head_train_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),

@@ -19,8 +19,8 @@ LIB = os.path.join(PKG, "libcfhip.so")
 
 ARCH = "gfx950"
 COMMON = os.environ.get("CF_EXTRA_FLAGS", "").split() + ["-O3", "-std=c++17", "-fPIC", f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}"]
-# (source, extra flags).  cf_topk / cf_frustum / cf_decode / cf_radar, the index path, must not fuse mul+add (bit-exact slice
-# bounds, gates and roundings).
+# (source, extra flags).  cf_topk / cf_frustum / cf_decode / cf_radar, the index path, and cf_targets must not fuse mul+add
+# (bit-exact slice bounds, gates and roundings).
 SOURCES = [
     ("cf_gemm.hip", []),
     ("cf_gemm_f16.hip", []),
@@ -36,6 +36,7 @@ SOURCES = [
     ("cf_decode.hip", ["-ffp-contract=off"]),
     ("cf_radar.hip", ["-ffp-contract=off"]),
     ("cf_loss.hip", []),
+    ("cf_targets.hip", ["-ffp-contract=off"]),
     ("cf_pack.cpp", ["-ffp-contract=off"]),     # host-side packers: the fp32 BN fold must round like torch's (no fused multiply-add)
     ("cf_error.cpp", []),
 ]

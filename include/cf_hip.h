@@ -716,6 +716,86 @@ size_t cf_head_bwd_workspace_bytes(int B, int h, int w, int Cin, int n_hidden, i
 /* the chunk length those calls use for this geometry and chunk_px (0: the default) */
 int cf_head_bwd_chunk_px(int B, int h, int w, int chunk_px);
 
+/* Training targets: the collated batch of the reference's dataset for B images, built on the device from packed annotation
+ * tables (csrc/cf_targets.hip; added under ABI 7, nothing existing changed).  replaces: the loop over annotations of
+ * dataset/generic_dataset.py:206-228, initReturn / transformBbox / addInstance / processAlpha (generic_dataset.py:441-708),
+ * nuScenes.initReturn (dataset/datasets/nuscenes.py:348-391), getGaussianRadius / getGaussianMatrix / ellip_gaussian2D /
+ * drawGaussianHeatRegion (utils/image.py:145-256), get3dBox (utils/ddd.py:8-23), and, on numpy inputs, cvtAlphaToYaw /
+ * get3DCorners / getDistanceThresh / cvtPcDepthToHeatmap (utils/pointcloud.py:214-328, 397-481).  One pyramid layer.
+ *
+ * Arithmetic follows numpy's dtypes operation by operation (float64 where numpy promotes, fp32 where it stores; a Python
+ * scalar next to an fp32 value stays fp32).  Rows are indexed by annotation: a skipped annotation (class id > C or <= -999,
+ * height or width <= 0 after the clip, index >= counts[b]) leaves a zero row.  Every element of every output is written; no
+ * output needs zeroing.  Optional outputs may be NULL (a head the configuration lacks). */
+#define CF_TARGETS_MAX_OBJS 128
+#define CF_TARGETS_F 20        /* float64 per annotation, see cf_targets_args.ann                                       */
+#define CF_TARGETS_DESC_BYTES 112 /* workspace bytes per (image, annotation)                                            */
+/* presence bits of the optional annotation keys (iann[..][2]) */
+#define CF_TARGETS_HAS_AMODAL 1
+#define CF_TARGETS_HAS_ATTRIBUTES 2
+#define CF_TARGETS_HAS_VELOCITY 4
+#define CF_TARGETS_HAS_ALPHA 8
+#define CF_TARGETS_HAS_DEPTH 16
+#define CF_TARGETS_HAS_DIMENSION 32
+#define CF_TARGETS_HAS_LOCATION 64
+#define CF_TARGETS_HAS_YAW 128
+/* cf_targets_args.flags */
+#define CF_TARGETS_REP3D 1       /* DATASET.HEATMAP_REP == "3d" (generic_dataset.py:581-588)                            */
+#define CF_TARGETS_NORM2D 2      /* MODEL.NORM_2D (generic_dataset.py:621-629)                                          */
+#define CF_TARGETS_WRITE_DEPTH 4 /* "depth" or "depth2" among the heads (generic_dataset.py:660)                        */
+#define CF_TARGETS_WRITE_ROT 8   /* "rotation" among the heads (generic_dataset.py:647)                                 */
+#define CF_TARGETS_FRUSTUM 16    /* DATASET.RADAR_PC and MODEL.FRUSTUM (generic_dataset.py:673-687)                     */
+
+typedef struct cf_targets_args {
+  const double* ann;     /* [B][M][CF_TARGETS_F]: bbox x, y, w, h (source pixels) | truncated | amodal_center x, y |
+                            velocity_cam[0..2], min(velocity_cam) | alpha | depth | dimension h, w, l | location x, y, z |
+                            yaw; an absent key is 0 with its presence bit clear                                        */
+  const int32_t* iann;   /* [B][M][3]: class id after the class map (1-based), attributes, presence bits              */
+  const int32_t* counts; /* [B]: annotations of the image that are looked at (<= M)                                    */
+  const double* trans;   /* [B][2][3]: source image -> output map (generic_dataset.py:182-187)                         */
+  const float* calib;    /* [B][3][4]; FRUSTUM only                                                                    */
+  const double* scale;   /* [B]: the augmentation's scale factor (depth * scale, generic_dataset.py:661)               */
+  const float* pc_dep;   /* [B][3][h][w] radar map, read only; FRUSTUM only                                            */
+  int32_t B, M, C, h, w; /* M <= CF_TARGETS_MAX_OBJS; (h, w) = MODEL.OUTPUT_SIZE                                       */
+  int32_t flags;         /* CF_TARGETS_*                                                                               */
+  float max_pc_dist;     /* DATASET.MAX_PC_DIST; FRUSTUM only                                                          */
+  float* heat;           /* [B][C][h][w]  heatmap0                                                                     */
+  int64_t* cls;          /* [B][M]        classIds (zero-based)                                                        */
+  float* mask;           /* [B][M]                                                                                     */
+  float* trunc_mask;     /* [B][M]                                                                                     */
+  float* wh;             /* [B][M][2]     widthHeight                                                                  */
+  float* reg;            /* [B][M][2]     or NULL                                                                      */
+  float* amodal_offset;  /* [B][M][2]     or NULL                                                                      */
+  float* dimension;      /* [B][M][3]     or NULL                                                                      */
+  float* depth;          /* [B][M][1]     or NULL                                                                      */
+  int64_t* rotbin;       /* [B][M][2]     or NULL; rotbin, rotres and t_rotation come together                         */
+  float* rotres;         /* [B][M][2]                                                                                  */
+  float* att;            /* [B][M][8]     nuscenes_att, or NULL; att and att_mask come together                        */
+  float* att_mask;       /* [B][M][8]     nuscenes_att_mask                                                            */
+  float* velocity;       /* [B][M][3]     or NULL                                                                      */
+  float* pc_hm;          /* [B][3][h][w]  FRUSTUM only: zero where no box paints                                       */
+  float* t_bboxes;       /* [B][M][4]     target.bboxes (x1, y1, x2, y2 on the output map)                             */
+  float* t_scores;       /* [B][M]        target.scores: zeros, as the reference leaves them                           */
+  float* t_centers;      /* [B][M][2]     target.centers                                                               */
+  float* t_heat_centers; /* [B][M][2]     target.heatCenters                                                           */
+  float* t_bboxes3d;     /* [B][M][8][3]  target.bboxes3d                                                              */
+  float* t_rotation;     /* [B][M][8]     target.rotation, or NULL                                                     */
+  float* t_att;          /* [B][M][8]     target.nuscenes_att: zeros (the reference never fills it), or NULL           */
+  float* t_velocity;     /* [B][M][3]     target.velocity: zeros, or NULL                                              */
+  void* workspace;       /* cf_targets_workspace_bytes(B, M) bytes, 8-byte aligned: the per-object descriptors         */
+  size_t workspace_bytes;
+} cf_targets_args;
+/* Three launches of 256 threads on `stream`, no host sync, bitwise reproducible:
+ *   objects   one thread per (image, annotation): every per-object row, plus a descriptor (class, integer centre, radii and
+ *             2 sigma^2, clipped Gaussian window, frustum ROI, paint rectangle, depth gate) in the workspace;
+ *   heat map  one workgroup per (16-row band, image): descriptors staged in LDS, those missing the band culled; each element
+ *             is the maximum over the objects of its class of the float64 Gaussian rounded to fp32, or 0;
+ *   frustum   (CF_TARGETS_FRUSTUM) one workgroup per (band, image): a wave per box whose paint rectangle reaches the band
+ *             finds the first row-major minimum among the non-zero radar pixels of its ROI with lo < v < hi; each pixel takes
+ *             v / max_pc_dist (fp32) and the two velocity channels of the LAST such box in annotation order that covers it. */
+int cf_targets_build(const cf_targets_args* a, void* stream);
+size_t cf_targets_workspace_bytes(int B, int M);
+
 /* Weight packing runs once per load_state_dict (BatchNorm fold, slot tables, split hi / lo planes, MFMA fragment order).
  * For the f16x3 convolution and DCN operators it is part of this ABI (cf_pack_conv_f16x3, cf_pack_dcn_f16 above: host-side C,
  * byte-identical to the Python packers); the heads', the stem's and the upsample's weights are packed by

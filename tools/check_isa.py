@@ -17,7 +17,8 @@ CSRC = os.path.join(ROOT, "centerfusiondetect3d_amd", "csrc")
 SOURCES = {"cf_conv3x3_f16.hip": ("conv3x3_f16x3_kernel",), "cf_heads.hip": ("head_patch16_kernel",),
            "cf_gemm_f16.hip": ("dcn_f16x3_kernel", "conv_f16x3_kernel"), "cf_frustum.hip": ("pc_hm_direct_kernel",),
            "cf_stem_early.hip": ("stem_early_kernel",),
-           "cf_dcn_bwd.hip": ("dcn_bwd_data_kernel", "dcn_bwd_weight_kernel")}
+           "cf_dcn_bwd.hip": ("dcn_bwd_data_kernel", "dcn_bwd_weight_kernel"),
+           "cf_targets.hip": ("targets_heat_kernel", "targets_frustum_kernel")}
 
 
 def functions(asm):
@@ -55,7 +56,8 @@ EPILOGUE_KERNELS = ("conv_f16x3_kernel", "dcn_f16x3_kernel", "conv3x3_f16x3_kern
 # kernels whose MFMA loop must be free of scratch traffic (every instantiation the default path launches)
 # kernels of the default path: NO instantiation may use scratch at all (ScratchSize 0 in the compiler's resource summary)
 NO_SCRATCH = ("head_patch16_kernel", "dcn_f16x3_kernel", "conv3x3_f16x3_kernel", "conv_f16x3_kernel",
-              "pc_hm_direct_kernel", "stem_early_kernel", "dcn_bwd_data_kernel", "dcn_bwd_weight_kernel", "dcn_bwd_reduce_kernel")
+              "pc_hm_direct_kernel", "stem_early_kernel", "dcn_bwd_data_kernel", "dcn_bwd_weight_kernel", "dcn_bwd_reduce_kernel",
+              "targets_object_kernel", "targets_heat_kernel", "targets_frustum_kernel")
 
 
 def scratch_sizes(asm):
