@@ -9,7 +9,12 @@ float64 and fp32, the case table and the two constructions that keep the ReLU ma
 
 Geometry the cases reach (the kernels' constants, restated here and asserted by the CPU test against the library): 32-position
 tiles of the layer kernel, 256-position slabs of the weight-gradient kernels, 128-position slabs of the output layer's, chunks
-that are multiples of 64 positions."""
+that are multiples of 64 positions; the three launch caps behind which a kernel loops (GEMM_GRID_CAP, OUT_BWD_GRID_CAP,
+OUT_FWD_THREAD_CAP).
+
+REPLICATED holds the sizes a direct reference cannot reach (the fp32 oracle's own error on a large dense gradient exceeds the
+rule's limit): a head is per-image, so R copies of a base batch give R copies of its float64 map, and the gradients are those of
+the few images that carry a dY - a small batch the float64 reference runs directly (`rep_reference`)."""
 import functools
 
 import torch
@@ -17,6 +22,12 @@ from torch import nn
 
 HID = 256
 TILE, SLAB, OUT_SLAB = 32, 256, 128
+DEFAULT_CHUNK = 32768            # cf_heads_bwd.hip:22
+# the launch caps of cf_heads_bwd.hip, kernel-internal (no entry point reports them): above them a kernel loops
+GEMM_GRID_CAP = 4096             # head_gemm_kernel: grid.x = min(tiles of a chunk, 4096); cf_heads_bwd.hip:447 and :551, loop at :61
+OUT_BWD_GRID_CAP = 4096          # head_out_bwd_data_kernel: grid = min(chunk, 4096) blocks, one position each; :539, loop at :325
+OUT_FWD_THREAD_CAP = 4096 * 256  # head_out_fwd_kernel: blocks_for(chunk * n_out, 4096) blocks of 256 threads; :503, loop at :303
+COMPACT_BLOCK = 256              # head_compact_kernel: pixels per block; :527
 
 # name: (B, c_x, c_x2, n_hidden, Cout, h, w, family, dY pattern, chunk_px, final)
 CASES = {
@@ -32,17 +43,67 @@ CASES = {
     "lin_two_chunks_c2":  (2, 64, 3, 2, 2, 17, 33, "linear", "dense", 576, None),       # 1122 positions: chunks of 576 and 546
     "lin_heatmap_c3":     (1, 64, 0, 0, 3, 5, 7, "linear", "dense", 0, "heatmap"),
     "lin_depth_c1":       (1, 64, 0, 0, 1, 5, 7, "linear", "dense", 0, "depth"),
+    # maps one pixel high / wide / both: two thirds (eight ninths) of the taps outside
+    "dy_1x40_c2":         (1, 64, 0, 0, 2, 1, 40, "dyadic", "dense", 0, None),
+    "dy_40x1_sec_c2":     (1, 64, 3, 2, 2, 40, 1, "dyadic", "dense", 0, None),
+    "dy_1x1_c3":          (2, 64, 0, 0, 3, 1, 1, "dyadic", "dense", 0, None),          # M = 2: only the centre tap inside
+    "dy_nh1_c4":          (2, 64, 3, 1, 4, 17, 33, "dyadic", "dense", 0, None),        # one hidden layer: odd parity of the g / g2 swap
+    "dy_cx72_sec_c3":     (1, 72, 3, 2, 3, 9, 11, "dyadic", "dense", 0, None),         # kvec = 64 < c_x = 72 < K = 75: the k-tail reads both rows
+    "dy_cx8_c2":          (1, 8, 0, 0, 2, 9, 11, "dyadic", "dense", 0, None),          # c_x < 16: kvec = 0
+    "lin_cin512_c2":      (1, 448, 64, 0, 2, 5, 7, "linear", "dense", 0, None),        # Cin at the limit: 16 channel chunks
+    "lin_8img_dense_c3":  (8, 64, 3, 2, 3, 17, 33, "linear", "dense", 0, None),        # 4488 positions in one chunk: above OUT_BWD_GRID_CAP
+    "lin_8img_5chunks_c2": (8, 64, 3, 2, 2, 17, 33, "linear", "dense", 1088, None),    # chunks 4 x 1088 + 136
+    "lin_8img_1500_c2":   (8, 64, 0, 0, 2, 17, 33, "linear", ("count", 1500), 1088, None),  # the list ends inside chunk 1; 2 .. 4 empty
+    "lin_8img_heat_c10":  (8, 64, 0, 0, 10, 17, 33, "linear", "dense", 0, "heatmap"),  # the workload's dense heat-map gradient
+    "lin_1img_nh1_c16":   (1, 64, 3, 1, 16, 17, 33, "linear", "dense", 0, None),       # the base of rep234_gridcaps
+}
+
+# name: (base case, R copies of the base's batch, chunk_px, {image of the replicated batch: its dY})
+# a dY is "base" (the base's dY of that image), "sparse" (the three pixels of the sparse pattern) or ("count", n) (n random pixels)
+REPLICATED = {
+    # M = 131274; one chunk of 131136 = 4098 tiles (> GEMM_GRID_CAP) x 16 outputs = 2.1 M elements (> OUT_FWD_THREAD_CAP), then 138
+    # positions; 33 + 3 + 561 = 597 list positions out of the first, a middle and the last of 513 compaction blocks
+    "rep234_gridcaps":     ("lin_1img_nh1_c16", 234, 131136, {0: ("count", 33), 117: "sparse", 233: "base"}),
+    # M = 35904 at the default chunk: 32768 + 3136, the boundary inside image 58
+    "rep64_default_chunk": ("lin_two_chunks_c2", 32, 0, {0: ("count", 33), 58: "base", 63: "base"}),
 }
 
 
+def _chunk(M, chunk_px):
+    return min(chunk_px or DEFAULT_CHUNK, (M + 63) // 64 * 64)
+
+
 def geometry(name):
-    """what the case reaches: positions, chunks, tiles of the last chunk, weight-gradient slabs (of a dense list)"""
-    B, _, _, _, _, h, w, _, pattern, chunk_px, _ = CASES[name]
+    """what the case reaches: positions, chunks, tiles of the last chunk, weight-gradient slabs (of a dense list); the chunk the
+    backward's list ends in, how far into it, and the chunks behind it that hold none of the list; the widths the first layer's
+    k loop sees on the packed sources `ops.head_stack` makes (K, and kvec: the leading channels read as vectors)"""
+    B, c_x, c_x2, n_hidden, cout, h, w, _, pattern, chunk_px, _ = CASES[name]
     M = B * h * w
-    chunk = min(chunk_px or 32768, (M + 63) // 64 * 64)
+    chunk = _chunk(M, chunk_px)
     n_act = M if pattern == "dense" else 0 if pattern == "zero" else 3 if pattern == "sparse" else pattern[1]
-    return dict(M=M, chunk=chunk, chunks=(M + chunk - 1) // chunk, active=n_act,
-                tiles=(min(n_act, chunk) + TILE - 1) // TILE, slabs=(min(n_act, chunk) + SLAB - 1) // SLAB)
+    chunks = (M + chunk - 1) // chunk
+    list_chunks = (n_act + chunk - 1) // chunk
+    return dict(M=M, chunk=chunk, chunks=chunks, active=n_act,
+                tiles=(min(n_act, chunk) + TILE - 1) // TILE, slabs=(min(n_act, chunk) + SLAB - 1) // SLAB,
+                list_end_chunk=list_chunks - 1, list_end_at=n_act - (list_chunks - 1) * chunk if n_act else 0,
+                empty_chunks=chunks - list_chunks, bwd_data_grid=min(chunk, OUT_BWD_GRID_CAP),
+                K=c_x + c_x2, kvec=c_x // 16 * 16 if c_x % 4 == 0 else 0, n_hidden=n_hidden,
+                taps_inside=min(h, 3) * min(w, 3))
+
+
+def rep_geometry(name):
+    """what a replicated case reaches: positions, the chunk, its tiles and output elements (the forward's two grid caps), the
+    backward's list and the compaction blocks it comes from, the images a forward chunk boundary falls strictly inside of"""
+    base, R, chunk_px, _ = REPLICATED[name]
+    B, _, _, _, cout, h, w = CASES[base][:7]
+    hw, M = h * w, R * B * h * w
+    chunk = _chunk(M, chunk_px)
+    dy = rep_build(name)["dy_full"]
+    at = (dy != 0).any(dim=1).flatten().nonzero().flatten()
+    return dict(M=M, images=R * B, chunk=chunk, chunks=(M + chunk - 1) // chunk, tiles=(chunk + TILE - 1) // TILE,
+                out_elems=chunk * cout, active=int(at.numel()), compact_blocks=(M + COMPACT_BLOCK - 1) // COMPACT_BLOCK,
+                active_blocks=sorted({int(v) // COMPACT_BLOCK for v in at}),
+                split_images=[c // hw for c in range(chunk, M, chunk) if c % hw])
 
 
 def _dyadic(gen, shape, step, lo, hi):
@@ -119,6 +180,61 @@ def build(name):
         dy = dy * keep
     return dict(x=x[:, :c_x].contiguous(), x2=x[:, c_x:].contiguous() if c_x2 else None, weights=weights, biases=biases, dy=dy,
                 final=final, chunk_px=chunk_px, checks=checks, family=family)
+
+
+@functools.lru_cache(maxsize=None)
+def rep_build(name):
+    """-> dict(base = the base case, images = the images that carry a dY, small = the case of just those images (float64, what
+    `run_reference` takes), dy_full = the replicated batch's dY (fp32, zero elsewhere), R, chunk_px).  The replicated sources
+    themselves are `rep_sources`' (not cached: 35 MB)."""
+    base_name, R, chunk_px, dys = REPLICATED[name]
+    base = build(base_name)
+    B, _, _, _, cout, h, w = CASES[base_name][:7]
+    gen = torch.Generator().manual_seed(sum(ord(c) * (i + 1) for i, c in enumerate(name)))
+    images, parts = sorted(dys), []
+    for img in images:
+        pattern = dys[img]
+        if pattern == "base":
+            d = base["dy"][img % B].clone()
+        else:
+            d = torch.randn((cout, h, w), generator=gen).float().double()
+            keep = torch.zeros(h * w, dtype=torch.float64)
+            if pattern == "sparse":
+                keep[0] = keep[h * w - 1] = keep[(h // 2) * w + w // 3] = 1.0
+            else:
+                keep[torch.randperm(h * w, generator=gen)[:pattern[1]]] = 1.0
+            d = d * keep.view(1, h, w)
+        parts.append(d)
+    dy_full = torch.zeros((R * B, cout, h, w), dtype=torch.float32)
+    dy_full[images] = torch.stack(parts).float()
+    pick = [i % B for i in images]
+    small = dict(x=base["x"][pick].contiguous(), x2=None if base["x2"] is None else base["x2"][pick].contiguous(),
+                 weights=base["weights"], biases=base["biases"], dy=torch.stack(parts), final=base["final"], chunk_px=0,
+                 family=base["family"])
+    return dict(base=base, images=images, small=small, dy_full=dy_full, R=R, chunk_px=chunk_px)
+
+
+def rep_sources(name):
+    """(x, x2 | None) of the replicated batch in fp32: R copies of the base's"""
+    rep = rep_build(name)
+    x, x2 = rep["base"]["x"].float(), rep["base"]["x2"]
+    return x.repeat(rep["R"], 1, 1, 1), None if x2 is None else x2.float().repeat(rep["R"], 1, 1, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def rep_reference(name):
+    """(float64 result, fp32 result) of the batch of just the images that carry a dY: its gradients are the replicated batch's"""
+    small = rep_build(name)["small"]
+    return run_reference(small, torch.float64), run_reference(small, torch.float32)
+
+
+def rep_oracle_errors(name):
+    """{label: error of the fp32 CPU oracle against float64}: "y" on the base case (every replica's map is the base's), the
+    gradients on the batch of the images that carry a dY"""
+    r64, r32 = rep_reference(name)
+    e = {k: rel_err(v32, v64) for (k, v64), (_, v32) in zip(quantities(r64), quantities(r32)) if k[0] == "g"}
+    e["y"] = oracle_errors(REPLICATED[name][0])["y"]
+    return e
 
 
 def final_act(y, final):

@@ -1,5 +1,5 @@
 """CPU side of the head training path: the constructions of tests/heads_train_ref.py hold what they promise, the cases reach the
-geometry they are named for, the fp32 oracle is usable on every case, `ops.head_stack` and `DLASeg` refuse what they do not
+geometry they are named for (the replicated ones too), the fp32 oracle is usable on every case, `ops.head_stack` and `DLASeg` refuse what they do not
 implement before any device is touched, construction sets the requires_grad flags, and the ctypes mirror of
 cf_head_train_args has the C compiler's layout."""
 import ctypes
@@ -59,6 +59,28 @@ def test_cases_reach_their_geometry():
     two = g["lin_two_chunks_c2"]
     assert two["chunks"] == 2 and two["chunk"] == 576 and two["M"] - two["chunk"] not in (0, two["chunk"])
     assert {T.CASES[n][4] for n in T.CASES} >= {1, 2, 3, 8, 10, 16}
+    # one-pixel-high / -wide maps, the depths, the widths of the first layer's k loop
+    assert g["dy_1x40_c2"]["taps_inside"] == 3 == g["dy_40x1_sec_c2"]["taps_inside"] and g["dy_1x1_c3"]["taps_inside"] == 1
+    assert g["dy_1x1_c3"]["M"] == 2 and g["dy_40x1_sec_c2"]["K"] == 67
+    assert {g[n]["n_hidden"] for n in T.CASES} == {0, 1, 2} and g["dy_nh1_c4"]["n_hidden"] == 1
+    cx72, cx8, c512 = g["dy_cx72_sec_c3"], g["dy_cx8_c2"], g["lin_cin512_c2"]
+    assert 0 < cx72["kvec"] == 64 < T.CASES["dy_cx72_sec_c3"][1] == 72 < cx72["K"] == 75        # the k-tail reads both sources
+    assert cx8["kvec"] == 0 and cx8["K"] == 8
+    assert c512["K"] == 512 and (c512["K"] + 31) // 32 == 16 and c512["kvec"] == 448
+    # a dense list above the grid of head_out_bwd_data_kernel, in one chunk
+    for n in ("lin_8img_dense_c3", "lin_8img_heat_c10"):
+        assert g[n]["chunks"] == 1 and g[n]["chunk"] == 4544 and g[n]["bwd_data_grid"] == T.OUT_BWD_GRID_CAP < g[n]["active"] == 4488
+    assert T.CASES["lin_8img_heat_c10"][4] == 10 and T.CASES["lin_8img_heat_c10"][10] == "heatmap"
+    # five chunks, the last ragged; a list that ends strictly inside chunk 1 with three empty chunks behind it
+    five, part = g["lin_8img_5chunks_c2"], g["lin_8img_1500_c2"]
+    assert five["chunks"] == 5 and five["chunk"] == 1088 and five["M"] - 4 * five["chunk"] == 136 and five["empty_chunks"] == 0
+    assert five["list_end_chunk"] == 4 and five["list_end_at"] == 136
+    assert part["chunks"] == 5 and part["list_end_chunk"] == 1 and 0 < part["list_end_at"] == 412 < part["chunk"]
+    assert part["empty_chunks"] == 3
+    # every earlier case is below the caps: the loops are reached by the cases named for them alone
+    assert max(g[n]["active"] for n in T.CASES if not n.startswith("lin_8img")) < T.OUT_BWD_GRID_CAP
+    assert max(g[n]["chunk"] * T.CASES[n][4] for n in T.CASES) <= T.OUT_FWD_THREAD_CAP
+    assert max(g[n]["chunk"] // T.TILE for n in T.CASES) <= T.GEMM_GRID_CAP
     # the dY patterns are what geometry() counts
     for n in T.CASES:
         dy = T.build(n)["dy"]
@@ -70,8 +92,46 @@ def test_cases_reach_their_geometry():
     lib = _lib.load()
     for n, (B, _, _, _, _, h, w, _, _, chunk_px, _) in T.CASES.items():
         assert lib.cf_head_bwd_chunk_px(B, h, w, chunk_px) == g[n]["chunk"]
+    for n, (base, R, chunk_px, _) in T.REPLICATED.items():
+        B, _, _, _, _, h, w = T.CASES[base][:7]
+        assert lib.cf_head_bwd_chunk_px(R * B, h, w, chunk_px) == T.rep_geometry(n)["chunk"]
     assert lib.cf_head_bwd_workspace_bytes(2, 17, 33, 67, 2, 576) < lib.cf_head_bwd_workspace_bytes(2, 17, 33, 67, 2, 0)
     assert lib.cf_head_train_workspace_bytes(2, 17, 33, 67, 2, 0) < lib.cf_head_bwd_workspace_bytes(2, 17, 33, 67, 2, 0)
+
+
+def test_replicated_cases_reach_their_geometry():
+    caps, dflt = T.rep_geometry("rep234_gridcaps"), T.rep_geometry("rep64_default_chunk")
+    # both forward grid caps bind in the first chunk, and a second chunk follows it
+    assert caps["M"] == 131274 and caps["chunk"] == 131136 and caps["chunks"] == 2 and caps["M"] - caps["chunk"] == 138
+    assert caps["tiles"] == 4098 > T.GEMM_GRID_CAP and caps["out_elems"] > T.OUT_FWD_THREAD_CAP
+    assert caps["chunk"] > T.GEMM_GRID_CAP * T.TILE                     # positions only the second pass of the loop reaches
+    # the list: 33 + 3 + 561 positions out of the first, a middle and the last of 513 compaction blocks
+    assert caps["active"] == 597 and caps["compact_blocks"] == 513
+    blocks = caps["active_blocks"]
+    assert blocks[0] == 0 and blocks[-1] == 512 and any(200 < b < 300 for b in blocks)
+    # the default chunk: 32768 + 3136, the boundary strictly inside image 58, which carries a gradient as do the first and last
+    assert dflt["M"] == 35904 and dflt["chunk"] == T.DEFAULT_CHUNK and dflt["chunks"] == 2 and dflt["M"] - dflt["chunk"] == 3136
+    assert dflt["split_images"] == [58] and T.rep_build("rep64_default_chunk")["images"] == [0, 58, 63] and dflt["images"] == 64
+    assert dflt["active"] == 33 + 2 * 561
+    for n in T.REPLICATED:
+        rep, (base, R, _, dys) = T.rep_build(n), T.REPLICATED[n]
+        B = T.CASES[base][0]
+        # the dY is zero outside the named images, fp32-representable, and the small batch is those images of the replicated one
+        live = (rep["dy_full"] != 0).flatten(1).any(dim=1).nonzero().flatten().tolist()
+        assert live == rep["images"] == sorted(dys)
+        assert torch.equal(rep["dy_full"][rep["images"]].double(), rep["small"]["dy"])
+        x, x2 = T.rep_sources(n)
+        assert x.shape[0] == R * B and torch.equal(x[rep["images"]].double(), rep["small"]["x"])
+        assert torch.equal(x.view(R, B, *x.shape[1:]), rep["base"]["x"].float().expand(R, *rep["base"]["x"].shape))
+        if x2 is not None:
+            assert torch.equal(x2[rep["images"]].double(), rep["small"]["x2"])
+        for img, pattern in dys.items():
+            n_act = int((rep["dy_full"][img] != 0).any(dim=0).sum())
+            assert n_act == (x.shape[2] * x.shape[3] if pattern == "base" else 3 if pattern == "sparse" else pattern[1])
+        # linear family: the masks cannot flip; the fp32 oracle is usable on every quantity (case_gate raises above 1.25e-5)
+        assert rep["base"]["family"] == "linear"
+        for label, e in T.rep_oracle_errors(n).items():
+            T.case_gate(e)
 
 
 def test_head_train_struct_layout_matches_c(tmp_path):
