@@ -21,6 +21,7 @@
 // accumulators) whose [64 px][256 ch] hi and lo planes (66 KiB) stay in LDS for the whole chain; in the output layer
 // the 4 waves split K instead and their partial sums are reduced through LDS.
 #include <stdlib.h>
+#include <string>
 #include "cf_common.h"
 #include "cf_mx.h"
 
@@ -103,6 +104,24 @@ struct TileMap {       // 64 pixels of a tile at (y0, x0) of image b: 4 rows of 
     if (y >= H || x >= W) return false;
     bb = b;
     pix = y * W + x;
+    return true;
+  }
+};
+
+// Virtual tiles (head_patch16_kernel<.., AT>): the 8 x 16 tile holds 3 x 6 disjoint 3x3 neighbourhoods whose centres - tile pixels
+// (row 0 / 3 / 6, column 0 / 3 / .. / 15) - are the slots of a per-tile table of flat map pixels b * HW + y * W + x (-1: empty)
+constexpr int AT_SLOTS = 18;
+__device__ __forceinline__ int at_slot_of(int ty, int tx) { return (ty % 3 == 0 && tx % 3 == 0) ? (ty / 3) * 6 + tx / 3 : -1; }
+struct SlotMap {       // 64 pixels of one half of a virtual tile: only the centres of non-empty slots are written
+  const int* slots;
+  int M, HW, half;
+  __device__ __forceinline__ bool operator()(int px, int& bb, int& pix) const {
+    const int t = half * 64 + px, sl = at_slot_of(t >> 4, t & 15);
+    if (sl < 0) return false;
+    const int s = slots[sl];
+    if ((unsigned)s >= (unsigned)M) return false;
+    bb = s / HW;
+    pix = s - bb * HW;
     return true;
   }
 };
@@ -266,6 +285,7 @@ struct HeadPatchK {
   const float* b_first[CF_MAX_HEADS];
   const unsigned char* w_out_perm[CF_MAX_HEADS];
   float first_scale[CF_MAX_HEADS];           // MX kernel: 2^-(s+4) of head i's first layer
+  const int* slot_pixels;                    // AT kernels: [tiles_x virtual tiles][AT_SLOTS] flat map pixels (-1: empty slot)
 };
 
 // MX = true: the FIRST layer on "fp16 main term + block-scaled FP6 cross terms" (1.5 MFMA passes per product instead of the 3
@@ -281,9 +301,14 @@ struct HeadPatchK {
 // first_scale = 2^-(s+4) where the bias is added.  Hidden and output layers: unchanged bf16x3.
 // HID: -1 = n_hidden decided at run time (the bf16x3 instantiations); 0 / 1 = compiled for heads without / with hidden layers
 // (the MX instantiations: the register allocator then sees one of the two epilogues, not both).
-template <int NS, bool PC, bool TP, bool MX = false, int HID = -1>
+// AT = true ("at the listed pixels"): the tile is a VIRTUAL one - 18 listed pixels of any images with their 3x3 neighbourhoods
+// gathered into the patch (SlotMap above; q.tiles_x tiles, q.tiles_y = 1) - and only those pixels of the maps are written.  Every
+// step between the patch fill and the output writes works per pixel column of the MFMA tile, so a pixel gets the bits the dense
+// form gives it.
+template <int NS, bool PC, bool TP, bool MX = false, int HID = -1, bool AT = false>
 __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
   static_assert(NS == 4, "64 feature channels");
+  static_assert(!AT || !TP, "virtual tiles are laid out on the flat 8 x 16 tile");
   constexpr int MX_SLAB = 14592, PC_OFF = MX ? 272 : NS * 64;      // (wave, tap) weight slab bytes; pc_hm planes inside a patch row
   // TP: the 128-pixel tile stands upright (16 rows x 8 columns) instead of 8 x 16 - same patch size (18 x 10 rows), chosen by
   // the host when it covers the map with fewer tiles (112 x 200: 7 x 25 = 175 exact tiles instead of 14 x 13 = 182)
@@ -305,7 +330,7 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
                                                                       : (lane & 3) * 4 + 2 + ((lane & 15) >> 3))
                               : (lane & 15);
   const int per_img = q.tiles_x * q.tiles_y;
-  const int per_head = per_img * (p.M / p.HW);
+  const int per_head = AT ? per_img : per_img * (p.M / p.HW);
   // grid = (head range, tile): a workgroup keeps its patch in LDS and walks q.hloop consecutive heads on it (heads
   // without hidden layers only: the hidden chain rewrites the patch area).  Head-range-major order, so the
   // workgroups in flight work on the same few heads and their first-layer weights stay hot in L2, while the patch
@@ -317,6 +342,24 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
   const int b = rem / per_img;
   rem -= b * per_img;
   const int y0 = (rem / q.tiles_x) * T_H, x0 = (rem % q.tiles_x) * T_W;
+  // AT: this workgroup's slots; patch row (pr, pc) of the 10 x 18 patch is neighbour (pr % 3 - 1, pc % 3 - 1) of slot (pr / 3, pc / 3)
+  // -> its flat map pixel, or -1 = a zero row (outside the image, an empty slot, the unused 10th patch row)
+  const int* const at_slots = AT ? q.slot_pixels + (size_t)rem * AT_SLOTS : nullptr;
+  auto at_src = [&](int row) -> int {
+    const int pr = row / P_W, pc = row % P_W;
+    if (pr >= 9) return -1;
+    const int s = at_slots[(pr / 3) * 6 + pc / 3];
+    if ((unsigned)s >= (unsigned)p.M) return -1;
+    const int bb = s / p.HW, pix = s - bb * p.HW;
+    const int y = pix / q.W + pr % 3 - 1, x = pix % q.W + pc % 3 - 1;
+    if ((unsigned)y >= (unsigned)q.H || (unsigned)x >= (unsigned)q.W) return -1;
+    return bb * p.HW + y * q.W + x;
+  };
+  if constexpr (AT) {                         // (workgroup-uniform) a tile without a listed pixel writes nothing
+    int any = 0;
+    for (int i = 0; i < AT_SLOTS; ++i) any |= (unsigned)at_slots[i] < (unsigned)p.M ? 1 : 0;
+    if (!any) return;
+  }
 
   // ---- patch -> LDS (one pass, every load in flight before the first LDS write)
   if constexpr (MX) {
@@ -329,6 +372,10 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       const int row = idx / UPR, u = idx % UPR;
       const int y = y0 - 1 + row / P_W, x = x0 - 1 + row % P_W;
       v[it] = u32x4{0u, 0u, 0u, 0u};                       // outside the image: zero fields with scale byte 0 (2^-127): exact zeros
+      if constexpr (AT) {
+        const int s = row < HP_ROWS ? at_src(row) : -1;
+        if (s >= 0) v[it] = *reinterpret_cast<const u32x4*>(q.src[0] + (size_t)s * 272 + u * 16);
+      } else
       if (row < HP_ROWS && (unsigned)y < (unsigned)q.H && (unsigned)x < (unsigned)q.W)
         v[it] = *reinterpret_cast<const u32x4*>(q.src[0] + (size_t)(b * p.HW + y * q.W + x) * 272 + u * 16);
     }
@@ -348,6 +395,11 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       const int row = idx / UPR, u = idx % UPR;
       const int y = y0 - 1 + row / P_W, x = x0 - 1 + row % P_W;
       v[it] = u32x4{0u, 0u, 0u, 0u};
+      if constexpr (AT) {
+        const int s = row < HP_ROWS ? at_src(row) : -1;
+        if (s >= 0) v[it] = *reinterpret_cast<const u32x4*>(q.src[0] + ((size_t)s * 2 * q.src_c[0]) * 2 +
+                                                             (u / (NS * 2)) * q.src_c[0] * 2 + (u % (NS * 2)) * 16);
+      } else
       if (row < HP_ROWS && (unsigned)y < (unsigned)q.H && (unsigned)x < (unsigned)q.W)
         v[it] = *reinterpret_cast<const u32x4*>(q.src[0] + ((size_t)(b * p.HW + y * q.W + x) * 2 * q.src_c[0]) * 2 +
                                                 (u / (NS * 2)) * q.src_c[0] * 2 + (u % (NS * 2)) * 16);
@@ -371,6 +423,10 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       const int row = idx >> 1, plane = idx & 1;
       const int y = y0 - 1 + row / P_W, x = x0 - 1 + row % P_W;
       u32x4 w = {0u, 0u, 0u, 0u};
+      if constexpr (AT) {
+        const int s = at_src(row);
+        if (s >= 0) w = *reinterpret_cast<const u32x4*>(q.src[1] + ((size_t)s * 2 + plane) * q.src_c[1] * 2);
+      } else
       if ((unsigned)y < (unsigned)q.H && (unsigned)x < (unsigned)q.W)
         w = *reinterpret_cast<const u32x4*>(q.src[1] + ((size_t)(b * p.HW + y * q.W + x) * 2 + plane) * q.src_c[1] * 2);
       *reinterpret_cast<u32x4*>(xt + row * ROWB + PC_OFF + plane * 16) = w;
@@ -664,7 +720,8 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       store_hidden_tile16<MX>(xt, a2, q.b_first[head], wave, lane, MX ? q.first_scale[head] : 1.0f, c16);
       if constexpr (MX) __builtin_amdgcn_sched_barrier(0);     // (the chain's first weight loads stay behind the tile stores)
       __syncthreads();
-      head_tail_from_lds16(p, xt, head, TileMap{b, y0 + (64 >> TSH) * half, x0, q.H, q.W, TSH});
+      if constexpr (AT) head_tail_from_lds16(p, xt, head, SlotMap{at_slots, p.M, p.HW, half});
+      else head_tail_from_lds16(p, xt, head, TileMap{b, y0 + (64 >> TSH) * half, x0, q.H, q.W, TSH});
       __syncthreads();
     }
     return;
@@ -740,14 +797,26 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
   {
     const int px = tid & (HP_PX - 1);
     const int y = y0 + (px >> TSH), x = x0 + (px & TMASK);
-    if (y < q.H && x < q.W) {
+    // this thread's pixel of the map: (image ob, pixel opix) - dense: the tile's own; AT: the slot's, for the centre pixels of
+    // non-empty slots
+    bool valid = y < q.H && x < q.W;
+    int ob = b;
+    size_t opix = (size_t)y * q.W + x;
+    if constexpr (AT) {
+      const int sl = at_slot_of(px >> 4, px & 15);
+      const int s = sl >= 0 ? at_slots[sl] : -1;
+      valid = (unsigned)s < (unsigned)p.M;
+      ob = s / p.HW;
+      opix = (size_t)(s - ob * p.HW);
+    }
+    if (valid) {
       const float* bo = p.b_out[head];
       float* out = p.out[head];
       float* out2 = p.out2[head];
       for (int n = tid >> 7; n < n_out; n += 2) {
         const float raw = red[n * HP_PX + px] + red[(16 + n) * HP_PX + px] + red[(32 + n) * HP_PX + px] +
                           red[(48 + n) * HP_PX + px] + bo[n];
-        const size_t o = ((size_t)b * n_out + n) * p.HW + (size_t)y * q.W + x;
+        const size_t o = ((size_t)ob * n_out + n) * p.HW + opix;
         float v = raw;
         if (act == CF_ACT_RELU) v = fmaxf(raw, 0.0f);
         else if (act == CF_ACT_SIGMOID_CLAMP) v = fminf(fmaxf(cf_sigmoid(raw), 1e-4f), 1.0f - 1e-4f);
@@ -839,9 +908,11 @@ constexpr int HEAD_MAX_K_PAD = 2048;   // bound of cf_head_fused_args.K_pad (64 
 #define CF_HEAD_FORMS "cf_head_fused runs layout3x3 = 1 (64-channel first source [, 8-channel second]) with mfma16 = 1 " \
                       "(16x16x32 fragments, n_out <= 16) only"
 
-extern "C" int cf_head_fused(const cf_head_fused_args* a, void* stream) {
-  CF_REQUIRE(a != nullptr, "cf_head_fused: null args");
+// slot_pixels == nullptr: the dense launch over the whole map; else n_tiles virtual tiles (cf_head_fused_at)
+static int head_fused_launch(const cf_head_fused_args* a, const int* slot_pixels, int n_tiles, void* stream) {
+  const bool at = slot_pixels != nullptr;
   HeadPatchK hp{};
+  hp.slot_pixels = slot_pixels;
   const int rc = fill_tail(&a->tail, hp.t);
   if (rc != CF_OK) return rc;
   CF_REQUIRE(a->n_src >= 1 && a->n_src <= 2, "cf_head_fused: n_src=%d", a->n_src);
@@ -896,12 +967,15 @@ extern "C" int cf_head_fused(const cf_head_fused_args* a, void* stream) {
   CF_REQUIRE(m16, CF_HEAD_FORMS ": nothing reads 32x32x16 fragments (mfma16 = 0)");
   bool portrait = t_port < t_land;
   if (const char* e = getenv("CF_HEAD_TILE")) portrait = atoi(e) != 0;
+  if (at) portrait = false;                  // (virtual tiles are flat)
   // workgroups whose pc_hm patch is all zero leave the pc_hm taps out (results do not depend on it; CF_HEAD_PC_SKIP = 0
   // runs them everywhere, for dev tools and tests)
   hp.pc_skip = 1;
   if (const char* e = getenv("CF_HEAD_PC_SKIP")) hp.pc_skip = atoi(e) != 0;
   hp.tiles_x = portrait ? (W + 7) / 8 : (W + 15) / 16;
   hp.tiles_y = portrait ? (H + 15) / 16 : (H + 7) / 8;
+  const int n_img = at ? 1 : a->tail.B;      // virtual tiles are not per image: the table holds flat pixels of the batch
+  if (at) { hp.tiles_x = n_tiles; hp.tiles_y = 1; }
   // heads without hidden layers: a workgroup walks several heads on one patch (chosen below; CF_HEAD_LOOP overrides
   // for dev tools).  With hidden layers the chain rewrites the patch: one head per workgroup.
   int hloop = 1;
@@ -914,7 +988,7 @@ extern "C" int cf_head_fused(const cf_head_fused_args* a, void* stream) {
       if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
       return 2 * (cus > 0 ? cus : 256);
     }();
-    const long tiles = (long)hp.tiles_x * hp.tiles_y * a->tail.B;
+    const long tiles = (long)hp.tiles_x * hp.tiles_y * n_img;
     const int n = n_heads, cand[3] = {1, 2, (n + 1) / 2};
     double best = 0.0;
     for (int i = 0; i < 3; ++i) {
@@ -927,7 +1001,8 @@ extern "C" int cf_head_fused(const cf_head_fused_args* a, void* stream) {
     if (hloop > n) hloop = n;
   }
   hp.hloop = hloop;
-  const long blocks = (long)hp.tiles_x * hp.tiles_y * a->tail.B * ((n_heads + hloop - 1) / hloop);
+  const long blocks = (long)hp.tiles_x * hp.tiles_y * n_img * ((n_heads + hloop - 1) / hloop);
+  CF_REQUIRE(blocks < (1L << 31), "%s: grid too large", at ? "cf_head_fused_at" : "cf_head_fused");
   const bool hidden = a->tail.n_hidden > 0;
   const bool pc = a->n_src == 2;
   const int lds = hp16_lds(pc, hidden);
@@ -935,7 +1010,18 @@ extern "C" int cf_head_fused(const cf_head_fused_args* a, void* stream) {
     lim.ensure(kernel, lds, hp16_lds(pc, false));
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, hp);
   };
-  static CfLdsLimit lim16[4], limx[4], limxh[2];
+  static CfLdsLimit lim16[4], limx[4], limxh[2], lim_at[4];
+  if (at) {
+    // the forms of the dense launch on virtual tiles (these instantiations may use scratch: a launch is one workgroup's
+    // lifetime long, not a throughput loop)
+    CF_REQUIRE(!mx || hidden == pc, "cf_head_fused_at: mx = 1 runs without hidden layers and pc_hm source, or with both (the forms "
+                                    "the model's head groups take); pack other heads for bf16x3");
+    if (mx && hidden) launch(head_patch16_kernel<4, true, false, true, 1, true>, lim_at[3]);
+    else if (mx) launch(head_patch16_kernel<4, false, false, true, 0, true>, lim_at[2]);
+    else if (pc) launch(head_patch16_kernel<4, true, false, false, -1, true>, lim_at[1]);
+    else launch(head_patch16_kernel<4, false, false, false, -1, true>, lim_at[0]);
+    return cf_check_launch("cf_head_fused_at");
+  }
   if (mx && hidden) {
     // (hidden layers behind an mx first layer WITHOUT the pc_hm source: that instantiation does not fit 256 registers
     //  without scratch, and no configuration of the reference has such heads - its packing stays bf16x3)
@@ -954,4 +1040,58 @@ extern "C" int cf_head_fused(const cf_head_fused_args* a, void* stream) {
     else launch(head_patch16_kernel<4, false, false>, lim16[0]);
   }
   return cf_check_launch("cf_head_fused");
+}
+
+extern "C" int cf_head_fused(const cf_head_fused_args* a, void* stream) {
+  CF_REQUIRE(a != nullptr, "cf_head_fused: null args");
+  return head_fused_launch(a, nullptr, 0, stream);
+}
+
+extern "C" int cf_head_fused_at(const cf_head_fused_args* a, const int32_t* slot_pixels, int n_tiles, void* stream) {
+  CF_REQUIRE(a != nullptr, "cf_head_fused_at: null args");
+  CF_REQUIRE(slot_pixels != nullptr && n_tiles > 0, "cf_head_fused_at: slot table missing or n_tiles=%d", n_tiles);
+  const int rc = head_fused_launch(a, slot_pixels, n_tiles, stream);
+  if (rc == CF_EINVAL) {                     // (the shared checks name cf_head_fused: say which entry point was called)
+    const std::string why = cf_last_error();
+    cf_set_error("cf_head_fused_at: %s", why.c_str());
+  }
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The slot tables of cf_head_fused_at from up to two (B, K) lists of pixel indices (the frustum chain's top-K, the decoder's
+// NMS peaks).  One thread per table entry.
+// ---------------------------------------------------------------------------------------------
+namespace {
+__global__ __launch_bounds__(256) void head_slot_tables_kernel(const int* __restrict__ tk, const int* __restrict__ pk, int B, int K,
+                                                               int HW, int* __restrict__ tp, int* __restrict__ ts) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int per_p = (2 * K + AT_SLOTS - 1) / AT_SLOTS * AT_SLOTS, per_s = (K + AT_SLOTS - 1) / AT_SLOTS * AT_SLOTS;
+  if (tp && i < B * per_p) {
+    const int b = i / per_p, j = i - b * per_p;
+    int v = -1;
+    if (j < K) v = tk ? tk[b * K + j] : -1;
+    else if (j < 2 * K) v = pk ? pk[b * K + j - K] : -1;
+    tp[i] = (unsigned)v < (unsigned)HW ? b * HW + v : -1;
+  }
+  if (ts && i < B * per_s) {
+    const int b = i / per_s, j = i - b * per_s;
+    const int v = (j < K && pk) ? pk[b * K + j] : -1;
+    ts[i] = (unsigned)v < (unsigned)HW ? b * HW + v : -1;
+  }
+}
+}  // namespace
+
+extern "C" int cf_head_slot_tables(const int32_t* list_a, const int32_t* list_b, int B, int K, int HW, int32_t* table_ab,
+                                   int32_t* table_b, void* stream) {
+  CF_REQUIRE(B > 0 && K > 0 && HW > 0, "cf_head_slot_tables: B=%d K=%d HW=%d", B, K, HW);
+  CF_REQUIRE((long)B * HW < (1L << 31), "cf_head_slot_tables: B * HW must stay below 2^31 (flat pixels are int32)");
+  CF_REQUIRE((long)B * (2L * K + AT_SLOTS) < (1L << 31), "cf_head_slot_tables: B * K too large");
+  CF_REQUIRE(list_a || list_b, "cf_head_slot_tables: no list");
+  CF_REQUIRE(table_ab || table_b, "cf_head_slot_tables: no table");
+  CF_REQUIRE(!table_b || list_b, "cf_head_slot_tables: table_b is built from list_b");
+  const long n = (long)B * ((2 * K + AT_SLOTS - 1) / AT_SLOTS * AT_SLOTS);   // (the larger table)
+  hipLaunchKernelGGL(head_slot_tables_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, list_a,
+                     list_b, B, K, HW, table_ab, table_b);
+  return cf_check_launch("cf_head_slot_tables");
 }

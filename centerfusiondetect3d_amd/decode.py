@@ -9,6 +9,7 @@ straight from the NCHW maps - the reference's ten full-map permute().contiguous(
 import torch
 
 from . import ops
+from .pending import PendingOutputs
 
 # column layout of the (B,K,33) detection tensor (== SURVEY.md §8(e) all-gather payload)
 DET_FIELDS = [("scores", 1), ("classIds", 1), ("centers", 2), ("bboxes", 4), ("rotation", 8),
@@ -24,7 +25,19 @@ def _peaks_and_maps(outputs, K):
     out = outputs[0]
     if "heatmap" not in out:
         return None
-    heat = out["heatmap"]
+    # A forward with model.heads_at_peaks hands out a PendingOutputs: every map but the heat map holds values at that forward's
+    # peaks only until someone reads it.  The decoder needs nothing else - provided it decodes exactly those peaks: the same K,
+    # and the heat map tensor the forward attached them to (nobody else can hold that tensor: reading it materialises).  It then
+    # reads through `peek`; in every other case the maps are materialised first.
+    get = out.get
+    if isinstance(out, PendingOutputs):
+        heat = out.peek("heatmap")
+        cached = getattr(heat, "_cf_peaks", None)
+        if out.pending and not (cached is not None and cached[0] == K and cached[1] == heat.data_ptr() and heat.is_contiguous()
+                                and not torch.cuda.is_current_stream_capturing()):
+            out.materialise()
+        get = out.peek
+    heat = get("heatmap")
     _, _, H, W = heat.shape
     # The forward may have computed exactly these peaks already, beside its own launches (plan._Plan.run: the heat map tensor
     # carries them with a checksum of the bits they were computed from).  They are used only for the very tensor object, and
@@ -41,13 +54,16 @@ def _peaks_and_maps(outputs, K):
         scores, inds, classes = ops.topk_peaks(heat, K, nms=True, out=(pk_s, pk_i, pk_c), only_if_changed=sums)
     else:
         scores, inds, classes = ops.topk_peaks(heat, K, nms=True)
-    depth = out.get("depth2", out.get("depth"))
+    depth = get("depth2", get("depth"))
     if "rotation2" in out:
-        out["rotation"] = out.pop("rotation2")
-    maps = {"reg": out.get("reg"), "wh": out.get("widthHeight"), "depth": depth,
-            "rot": out.get("rotation"), "dim": out.get("dimension"),
-            "amodal": out.get("amodal_offset"), "att": out.get("nuscenes_att"),
-            "vel": out.get("velocity")}
+        if isinstance(out, PendingOutputs):
+            out.rename("rotation2", "rotation")
+        else:
+            out["rotation"] = out.pop("rotation2")
+    maps = {"reg": get("reg"), "wh": get("widthHeight"), "depth": depth,
+            "rot": get("rotation"), "dim": get("dimension"),
+            "amodal": get("amodal_offset"), "att": get("nuscenes_att"),
+            "vel": get("velocity")}
     present = ["scores", "classIds", "centers"]
     for name, key in (("bboxes", "wh"), ("rotation", "rot"), ("dimension", "dim"),
                       ("amodal_offset", "amodal"), ("nuscenes_att", "att"), ("velocity", "vel"),
@@ -57,7 +73,7 @@ def _peaks_and_maps(outputs, K):
     # `uncertainty` (TRAIN.UNCERTAINTY_LOSS): the gather launch multiplies the score it WRITES by exp(-exp(u)) at the peak
     # (model/decode.py:80-85).  `scores` may be the buffer the forward attached to the heat map, shared by every later decode
     # of that tensor, so it is only ever read: a second decode weights the same raw scores again.
-    return scores, inds, classes, maps, H, W, present, out.get("uncertainty")
+    return scores, inds, classes, maps, H, W, present, get("uncertainty")
 
 
 def decode_packed(outputs, outputSize=(112, 200), K=100, norm2d=False):

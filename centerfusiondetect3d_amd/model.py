@@ -23,7 +23,7 @@ from torch import nn
 
 from . import _lib, ops, packing
 from .packing import Source
-from .plan import SECONDARY_HEADS, _Plan, feat_operand
+from .plan import AT_TIMED, SECONDARY_HEADS, _Plan, feat_operand
 from .streams import (_CAPTURE_LOCK, _PROBE_LOG, _PROBE_US, _SIDE_STREAMS,     # (tests and tools reach these through this module)
                       _concurrent, _pick_streams, _side_streams)
 
@@ -222,6 +222,10 @@ class DLASeg(nn.Module):
                                           # in the two-stream step the two launches are 0.024 ms faster (round 5, 6 of 6 A/B pairs)
         self.heads_lanes = True  # fused heads: the decoder's NMS + top-k on a side stream beside the frustum path and the secondary
                                  # launch (plan.py: _Plan._build_heads), handed to decode.py with the heat map
+        self.heads_at_peaks = True  # eval forwards (fused heads, heads_lanes, no stream capture): only the heat-map head runs over the
+                                    # whole map; the other heads are evaluated at the pixels the frustum association and the decoder
+                                    # read (cf_head_fused_at) and the returned dict computes the full maps on first read
+                                    # (pending.PendingOutputs; same bits either way).  False: every head over every pixel
         self.peaks_behind_frustum = True  # heads_lanes on a radar model: the decoder's lane starts behind the frustum chain instead of
                                           # behind the primary head launch (False: round 5's order; same results)
         self.frustum_fused = True  # radar: top-k of the raw heat map + frustum association as cf_topk_frustum (2 launches, the merge in the
@@ -889,6 +893,7 @@ class DLASeg(nn.Module):
             return _Plan(self, B, H, W, dev, part="heads", feat=feat, feat_in=feat_in)
 
         hplan = self._plan((B, H, W, dev, sid, "heads", n), heads_plan, store)
+        hplan.flush_pending()                              # (unread at-peaks outputs need the feature buffers the trunks are about to overwrite)
         if self.isEarly:
             # early fusion: the in-place normalisation (base_model.py:69-79) once, for the whole batch, on the caller's stream in
             # front of the forks; each trunk's stem reads its sub-batch's slice of the normalised map
@@ -962,6 +967,8 @@ class DLASeg(nn.Module):
         """Bracket EVERY launch of every plan with HIP events (dev tool: tools/layer_times.py)."""
         for plan in self._all_plans():
             plan.timed = {i: [] for i in range(len(plan.steps))} if on else {}
+            if on and plan.at is not None:
+                plan.timed.update({k: [] for k in AT_TIMED})      # (the launches an at-peaks forward adds behind tails.primary)
 
     def all_launch_times(self):
         """-> [(step name or kernel entry point, mean ms, algorithmic FLOPs)] in launch order (single-plan forward)."""
@@ -976,10 +983,17 @@ class DLASeg(nn.Module):
             ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
             nm = names.get(i, step[0].__name__)
             out.append((nm, ms, plan.step_flops.get(names.get(i, ""), 0.0)))
+            if nm == "tails.primary":
+                for k in AT_TIMED:
+                    ev = plan.timed.get(k, [])
+                    if ev:
+                        out.append((k, sum(a.elapsed_time(b) for a, b in ev) / len(ev), plan.step_flops.get(k, 0.0)))
         return out
 
     def conv_flops_per_forward(self):
-        """Algorithmic FLOPs (2*MACs) of all conv / DCN launches of one forward (the plans in use)."""
+        """Algorithmic FLOPs (2*MACs) of all conv / DCN / head launches of one forward (the plans in use), as the LAST forward
+        of each plan issued them: after an at-peaks forward (heads_at_peaks) the head groups count the pixels they were
+        evaluated at (`tails.*`, `at.primary`), after a dense one every pixel."""
         return sum(sum(p.step_flops.values()) for p in self._all_plans())
 
 

@@ -2,15 +2,19 @@
 every launch pre-built, a forward pass = the flat list `steps` issued on the caller's stream (and, with lanes, one side
 stream).  Built from a `DLASeg` (knobs, packed weights, pre-scales); the finished plan keeps no reference to the model."""
 import ctypes as C
+import weakref
 from typing import Dict, List
 
 import torch
 
 from . import _lib, ops, packing
+from .pending import PendingOutputs
 from ._lib import (ACT_NONE, ACT_RELU, ACT_SIGMOID_CLAMP, ACT_RAW_AND_SIGDEPTH, LAYOUT_NHWC, LAYOUT_NCHW)
 from .streams import _side_streams
 
 SECONDARY_HEADS = ["velocity", "nuscenes_att", "depth2", "rotation2"]   # detectHeads.py:146-153
+AT_SLOTS = 18                                  # pixels per virtual tile of cf_head_fused_at (include/cf_hip.h)
+AT_TIMED = ("at.topk", "at.peaks", "at.tables", "at.primary")   # `timed` keys of the launches an at-peaks forward adds
 
 
 def feat_operand(model):
@@ -73,6 +77,9 @@ class _Plan:
         self.pc_hm4 = self.pc_hm8 = None
         self.tk_scores = self.tk_inds = self.tk_cls = self.tk_ws = None
         self.pk_ws = self.ev_peaks = None
+        # heads at the peaks (model.heads_at_peaks, _build_at): the launch blocks and slot tables, (tail block, index) of every
+        # primary head in the split blocks, per group (dense FLOPs, FLOPs per pixel), the last pending outputs (weak)
+        self.at, self.at_tails, self.group_flops, self.group_srcs, self._last = None, {}, {}, {}, None
         self.feat, self.feat_in = feat, feat_in
         self._m, self._pk = model, model._packed     # for the builders only: a finished plan must not hold the model
         try:                                         # (model -> _plans -> plan -> model would leave a dropped plan set to the collector)
@@ -394,16 +401,37 @@ class _Plan:
         self._add(f"heads.{h}.out", 2.0 * B * h4 * w4 * pc.n * 256, (self.lib.cf_conv2d_fused, C.byref(a)), a)
         self.outs[h] = a
 
-    def _fused_heads(self, name, names, srcs, strides):
-        """One cf_head_fused launch: 3x3 + ReLU + tail for sibling heads, hidden never in HBM."""
+    def _head_block(self, name, names, srcs, strides):
+        """-> (argument block of heads `names` of the packed group `name`, their algorithmic FLOPs per pixel)"""
         B, h4, w4, heads = self.B, self.h4, self.w4, self._m.config.heads
         hd = [dict(self._pk[name][h], act=act_of(h)) for h in names]
         f = ops.head_fused_args(srcs, strides, hd[0].get("slots"), hd[0].get("k_pad", 0), B, h4, w4, hd)
+        self.keep.append(f)
+        return f, sum(2.0 * 256 * (9 * sum(d["real_cin"]) + 256 * len(d["w_hidden"]) + heads[h]) for h, d in zip(names, hd))
+
+    def _fused_heads(self, name, names, srcs, strides):
+        """One cf_head_fused launch: 3x3 + ReLU + tail for sibling heads, hidden never in HBM."""
+        f, px_flops = self._head_block(name, names, srcs, strides)
         for n, h in enumerate(names):
             self.tails[h] = (f.tail, n)
-        flops = sum(2.0 * B * h4 * w4 * 256 * (9 * sum(d["real_cin"]) + 256 * len(d["w_hidden"]) + heads[h])
-                    for h, d in zip(names, hd))
+        flops = self.B * self.h4 * self.w4 * px_flops
+        self.group_flops[name] = (flops, px_flops, f)
+        self.group_srcs[name] = list(srcs)
         self._add(name, flops, (self.lib.cf_head_fused, C.byref(f)), f)
+
+    def _build_at(self, feat_in):
+        """model.heads_at_peaks: what an at-peaks forward launches instead of the dense head groups (see run).  The heat-map head
+        alone in a block of its own (dense: the NMS and both top-K passes read every pixel), the other primary heads in a second
+        block, the slot tables of cf_head_fused_at: `tab_b` from the decoder's peaks, `tab_ab` (frustum association only) from
+        the frustum chain's top-K followed by the decoder's peaks.  The chained / secondary groups reuse their dense blocks."""
+        B, K, primary = self.B, self.K, self.primary
+        f_hm, px_hm = self._head_block("tails.primary", primary[:1], [feat_in], [64])
+        f_rest, px_rest = self._head_block("tails.primary", primary[1:], [feat_in], [64])
+        self.at_tails = {primary[0]: (f_hm.tail, 0), **{h: (f_rest.tail, n) for n, h in enumerate(primary[1:])}}
+        tiles_b, tiles_ab = -(-K // AT_SLOTS), -(-2 * K // AT_SLOTS)
+        self.at = dict(f_hm=f_hm, flops_hm=B * self.h4 * self.w4 * px_hm, f_rest=f_rest, px_rest=px_rest,
+                       tab_b=self._buf(B * tiles_b * AT_SLOTS, dtype=torch.int32), n_b=B * tiles_b,
+                       tab_ab=self._buf(B * tiles_ab * AT_SLOTS, dtype=torch.int32) if self.frustum else None, n_ab=B * tiles_ab)
 
     def _peaks_lane(self):
         """the side lane: starts behind whatever the caller's stream has issued so far, runs the decoder's NMS + top-k"""
@@ -504,6 +532,10 @@ class _Plan:
                     self._head_out(h, s1, ss)
         if split:
             self.ctl("wait", 0, self.ev_peaks)
+        # heads at the peaks: fused heads whose plan computes the decoder's peaks in the forward (heads_lanes; without it the
+        # forward runs dense: the decoder then computes its peaks itself, after the forward)
+        if split and len(primary) > 1:
+            self._build_at(feat_in)
 
     # ------------------------------------------------------------------------------------------ issue
     def add_step(self, step):
@@ -529,15 +561,17 @@ class _Plan:
         ev.append((e0, e1))
         return rc
 
-    def _launch(self, st):
-        """Issue the plan's steps.  With lanes (and outside a stream capture) a step runs on the caller's stream (lane 0) or
+    def _launch(self, st, seq=None):
+        """Issue the plan's steps (seq: another launch list [(key in `timed`, step, lane)], the at-peaks forward's).  With lanes (and outside a stream capture) a step runs on the caller's stream (lane 0) or
         on the plan's side stream (lane 1), ordered by the ("rec" | "wait", event) control steps; otherwise everything runs
         in list order on the caller's stream (the list order is a valid sequential order).  Timed steps (model.time_launch)
         are bracketed by HIP events recorded on the stream the step runs on."""
         lanes_on = self.use_lanes and not torch.cuda.is_current_stream_capturing()
         timed = self.timed
+        if seq is None:
+            seq = zip(range(len(self.steps)), self.steps, self.lanes)
         if not lanes_on:
-            for i, step in enumerate(self.steps):
+            for i, step, _ in seq:
                 if isinstance(step[0], str):
                     continue                                   # one stream: program order is the dependency order
                 ev = timed.get(i) if timed else None
@@ -551,7 +585,7 @@ class _Plan:
             self._events = [torch.cuda.Event() for _ in range(self.n_events)]
         streams = (cur, self._side)
         ptrs = (st, self._side.cuda_stream)
-        for i, (step, lane) in enumerate(zip(self.steps, self.lanes)):
+        for i, step, lane in seq:
             op = step[0]
             if op == "rec":
                 self._events[step[1]].record(streams[lane])
@@ -602,15 +636,24 @@ class _Plan:
         st = _lib.stream_ptr()
         h4, w4 = self.h4, self.w4
         heads = model.config.heads
-        y = {}
+        self.flush_pending()                               # (before anything the last forward's maps depend on is patched or overwritten)
+        # at the peaks: eval forwards outside a stream capture (the training forward never comes here; a capture, and with it
+        # model.use_graph, records the dense launches)
+        at = self.at if (self.at is not None and getattr(model, "heads_at_peaks", True)
+                         and not torch.cuda.is_current_stream_capturing()) else None
+        y, written = {}, []                                # written: every tensor a head launch of this forward writes
         new = alloc or (lambda c: torch.empty((B, c, h4, w4), device=dev, dtype=torch.float32))
 
         def out(h, c, second=False):
             """a (B, c, h4, w4) output tensor, patched into head h's argument block (second: its `out2`)"""
             t = new(c)
+            written.append(t)
             if h in self.tails:
                 a, n = self.tails[h]
                 (a.out2 if second else a.out)[n] = t.data_ptr()
+                if h in self.at_tails:                     # (the split primary blocks of the at-peaks forward)
+                    a, n = self.at_tails[h]
+                    (a.out2 if second else a.out)[n] = t.data_ptr()
             elif second:
                 self.outs[h].out2 = t.data_ptr()
             else:
@@ -635,9 +678,10 @@ class _Plan:
                 pk_c = torch.empty((B, K), device=dev, dtype=torch.int32)
                 pk_sum = torch.empty(2 * ops.CHECKSUM_PARTS, device=dev, dtype=torch.int64)   # checksum parts of the map the peaks belong to | decode's re-check
                 n_words = B * heads["heatmap"] * h4 * w4
-                self.steps[self.peaks_step] = (_peaks_and_checksum, lib, (hm.data_ptr(), B, heads["heatmap"], h4, w4, K, 2,
-                                               pk_s.data_ptr(), pk_i.data_ptr(), pk_c.data_ptr(), self.pk_ws.data_ptr()),
-                                               (hm.data_ptr(), C.c_long(n_words), pk_sum.data_ptr()))
+                peaks = (_peaks_and_checksum, lib, (hm.data_ptr(), B, heads["heatmap"], h4, w4, K, 2,
+                         pk_s.data_ptr(), pk_i.data_ptr(), pk_c.data_ptr(), self.pk_ws.data_ptr()),
+                         (hm.data_ptr(), C.c_long(n_words), pk_sum.data_ptr()))
+                self.steps[self.peaks_step] = peaks if at is None else (_no_launch,)   # (at the peaks: in line, see _at_seq)
             else:
                 self.steps[self.peaks_step] = (_no_launch,)
         if self.direct_step is not None:
@@ -658,13 +702,24 @@ class _Plan:
                 geom = (y["depth"].data_ptr(), y["widthHeight"].data_ptr(), y["dimension"].data_ptr(), y["rotation"].data_ptr(),
                         calib.data_ptr(), pc_dep.data_ptr(), B, h4, w4, max_dist, pc_hm.data_ptr(), *maps)
                 tk = (self.tk_scores.data_ptr(), self.tk_inds.data_ptr(), self.tk_cls.data_ptr(), self.tk_ws.data_ptr())
-                if self.topk_step is None:
+                if at is not None:                         # the top-K runs in front of the at-peaks launch that feeds the association
+                    if self.topk_step is not None:
+                        self.steps[self.topk_step] = (_no_launch,)
+                    self.steps[self.frustum_step] = (lib.cf_frustum_assoc, self.tk_inds.data_ptr(), K, *geom)
+                elif self.topk_step is None:
                     self.steps[self.frustum_step] = (lib.cf_topk_frustum, hm.data_ptr(), heads["heatmap"], K, *geom, *tk)
                 else:
                     self.steps[self.topk_step] = (lib.cf_topk_peaks, hm.data_ptr(), B, heads["heatmap"], h4, w4, K, 0, *tk)
                     self.steps[self.frustum_step] = (lib.cf_frustum_assoc, self.tk_inds.data_ptr(), K, *geom)
             self._radar_outputs(y, out, heads, pc_dep, pc_hm)
-        self._launch(st)
+        for name, (flops, px_flops, _) in self.group_flops.items():    # FLOPs of the launch each named step issues THIS forward
+            self.step_flops[name] = flops
+        if at is None:
+            self._launch(st)
+        else:
+            topk = (lib.cf_topk_peaks, hm.data_ptr(), B, heads["heatmap"], h4, w4, K, 0, *tk) if self.frustum else None
+            self._launch(st, self._at_seq(at, peaks, topk, pk_i))
+            y = self._pending(y, model, written)
         if self.peaks_step is not None and peaks_on:
             # (decode.py re-checks the map's contents against pk_sum[0] on the device before it trusts the peaks)
             hm._cf_peaks = (K, hm.data_ptr(), pk_s, pk_i, pk_c, pk_sum)
@@ -672,6 +727,93 @@ class _Plan:
                 for t in (hm, pk_s, pk_i, pk_c, pk_sum):
                     t.record_stream(self._side)
         return [y]
+
+    # ------------------------------------------------------------------------------------------ heads at the peaks
+    def _at_seq(self, at, peaks, topk, pk_i):
+        """The launch list of an at-peaks forward: the plan's steps with the head groups replaced.  `tails.primary` = the dense
+        heat-map head (cf_head_fused on that head alone), followed IN LINE by the frustum chain's top-K (`topk`, frustum models),
+        the decoder's NMS + top-K + checksum (`peaks`; its lane stays empty), the slot tables and the other primary heads at the
+        listed pixels; `tails.chained` / `tails.secondary` = those groups at the decoder's peaks (cf_head_fused_at).  The step
+        FLOPs under the three names are set to what these launches compute.  (The decoder's pass on the side lane beside the
+        chain's top-K, joined in front of the tables, measured no faster: docs/experiments/heads_at_peaks.md.)"""
+        lib, idx = self.lib, self.step_index
+        tab_b, n_b = at["tab_b"].data_ptr(), at["n_b"]
+        tab_p, n_p = (at["tab_ab"].data_ptr(), at["n_ab"]) if self.frustum else (tab_b, n_b)
+        HP_PX = 128                                        # pixel columns a virtual tile computes (18 of them are written)
+        extra = ([("at.topk", topk, 0)] if topk is not None else []) + [("at.peaks", peaks, 0)]
+        extra += [
+                  ("at.tables", (lib.cf_head_slot_tables, self.tk_inds.data_ptr() if self.frustum else None, pk_i.data_ptr(),
+                                 self.B, self.K, self.h4 * self.w4, at["tab_ab"].data_ptr() if self.frustum else None, tab_b), 0),
+                  ("at.primary", (lib.cf_head_fused_at, C.byref(at["f_rest"]), tab_p, n_p), 0)]
+        repl = {idx["tails.primary"]: (lib.cf_head_fused, C.byref(at["f_hm"]))}
+        self.step_flops["tails.primary"] = at["flops_hm"]
+        self.step_flops["at.primary"] = n_p * HP_PX * at["px_rest"]
+        for name in ("tails.chained", "tails.secondary"):
+            if name in idx:
+                _, px_flops, f = self.group_flops[name]
+                repl[idx[name]] = (lib.cf_head_fused_at, C.byref(f), tab_b, n_b)
+                self.step_flops[name] = n_b * HP_PX * px_flops
+        seq = []
+        for i, (step, lane) in enumerate(zip(self.steps, self.lanes)):
+            seq.append((i, repl.get(i, step), lane))
+            if i == idx["tails.primary"]:
+                seq += extra
+        return seq
+
+    def _pending(self, y, model, written):
+        """The outputs of an at-peaks forward as a PendingOutputs.  Its materialiser runs the dense head launches from PRIVATE
+        copies of the groups' argument blocks (the pointers of this forward's output tensors are in them) on the forward's
+        stream, and orders the reading stream behind them.  Until the next forward of this plan the blocks read the plan's own
+        operand buffers (the heads' feature rows, the radar planes); that forward calls `release` first (flush_pending), which
+        copies those buffers - one pass over ~110 MB at bs 16, tens of microseconds - and points the blocks at the copies: a
+        dict held across later forwards stays pending, and complete."""
+        fwd = torch.cuda.current_stream(self.device)
+        lib, dev = self.lib, self.device
+        names = [n for n in ("tails.primary", "tails.chained", "tails.secondary") if n in self.step_index]
+        blocks = []
+        for n in names:
+            f = self.group_flops[n][2]
+            c = _lib.HeadFusedArgs()
+            C.memmove(C.byref(c), C.byref(f), C.sizeof(f))
+            blocks.append(c)
+        bufs = {t.data_ptr(): t for n in names for t in self.group_srcs[n]}
+        # (alive as long as the outputs are pending: every tensor the dense launches write - also one the dict does not hand out,
+        #  a radar model's raw `depth` logits -, the operand buffers or their copies, the plan that owns the former - the model
+        #  may drop it, or be dropped itself - and the packed weights the blocks point to)
+        keep = [written, list(y.values()), self, model._packed, bufs]
+
+        def materialise():
+            with torch.cuda.device(dev):                   # (under the model's lock: PendingOutputs takes it)
+                for c in blocks:
+                    rc = lib.cf_head_fused(C.byref(c), fwd.cuda_stream)
+                    if rc != 0:
+                        _lib.check(rc, "cf_head_fused")
+                rd = torch.cuda.current_stream(dev)
+                if rd != fwd:
+                    rd.wait_stream(fwd)
+            keep.clear()
+
+        def release():
+            with torch.cuda.device(dev), torch.cuda.stream(fwd):
+                for ptr, t in list(bufs.items()):
+                    snap = t.clone()
+                    for c in blocks:
+                        for i in range(c.n_src):
+                            if c.src[i] == ptr:
+                                c.src[i] = snap.data_ptr()
+                    bufs[ptr] = snap
+            keep[2] = None                                 # (the plan's buffers are no longer read)
+
+        p = PendingOutputs(y, materialise, model._lock, release)
+        self._last = weakref.ref(p)
+        return p
+
+    def flush_pending(self):
+        """The last at-peaks forward's outputs, if someone still holds them unread, stop depending on this plan's buffers: the
+        next forward is about to overwrite them (PendingOutputs.release: a copy of the operand buffers; never a wrong map)."""
+        last, self._last = (self._last() if self._last is not None else None), None
+        if last is not None:
+            last.release()
 
 
 def _early_input(x, pc, x8, stream):

@@ -301,6 +301,22 @@ typedef struct cf_head_fused_args {
 } cf_head_fused_args;
 int cf_head_fused(const cf_head_fused_args* a, void* stream);
 
+/* cf_head_fused_at: cf_head_fused at LISTED pixels only (no new struct, ABI 7): the same argument block, evaluated on n_tiles
+ * "virtual tiles" of 18 pixels each.  slot_pixels: [n_tiles][18] int32 in device memory, each entry a flat pixel
+ * b * H * W + y * W + x of the (B, ., H, W) maps, or anything outside [0, B * H * W) (-1 by convention) for an empty slot.
+ * For every listed pixel the launch writes, into `out[]` / `out2[]`, exactly the bits cf_head_fused writes there (the 3x3
+ * neighbourhood of the pixel is gathered from src[], zero outside its image); no other element of the maps is touched.
+ * Duplicates are allowed (the same bits are then written twice).  Grid: n_tiles x head groups - a launch far below one
+ * round of workgroups.  Forms: mx = 0 with or without hidden layers and pc_hm source; mx = 1 without both or with both.
+ * cf_head_slot_tables: one launch that builds such tables from up to two (B, K) lists of pixel indices in [0, H * W)
+ * (cf_topk_peaks' `inds`): table_ab [B][ceil(2K / 18)][18] from list_a (entries 0..K-1 of an image; NULL: empty) followed by
+ * list_b (entries K..2K-1), table_b [B][ceil(K / 18)][18] from list_b alone.  Either table may be NULL.  Every entry in
+ * [0, HW) gets a slot, entries outside get -1, the padding up to a whole tile is -1.  No reference counterpart: the
+ * reference evaluates every head at every pixel (model/networks/detectHeads.py:117-191) and reads them at the peaks. */
+int cf_head_fused_at(const cf_head_fused_args* a, const int32_t* slot_pixels, int n_tiles, void* stream);
+int cf_head_slot_tables(const int32_t* list_a, const int32_t* list_b, int B, int K, int HW, int32_t* table_ab,
+                        int32_t* table_b, void* stream);
+
 /* cf_pack_feat_mx: fp32 NHWC feature map [M][in_stride] (64 channels used) -> [M][272] bytes for cf_head_fused with mx = 1:
  * per pixel four 64-byte segments g = 0..3 - [8 fp16: hi channels 8g..8g+7][8 fp16: hi channels 32+8g..32+8g+7][FP6 block g:
  * 32 e2m3 fields (element j in bits 6j..6j+5, 24 B) + 8 B zero], block 0 / 1 = lo channels 0-31 / 32-63, block 2 / 3 = hi

@@ -13,6 +13,7 @@ ap.add_argument("--no-precise", action="store_true")
 ap.add_argument("--fp32-convs", action="store_true")
 ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--heads-bf16x3", action="store_true", help="heads' first layers on bf16x3 instead of fp16 + FP6 (A/B)")
+ap.add_argument("--dense-heads", action="store_true", help="every head over every pixel (model.heads_at_peaks = False; A/B)")
 ap.add_argument("--no-proj-fuse", action="store_true", help="the `project` convolutions as their own launches (A/B)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -25,7 +26,8 @@ m.heads_mx = not a.heads_bf16x3
 m.proj_fuse = not a.no_proj_fuse
 m.streams = 1          # per-launch event timing needs one stream
 m.lanes = False
-m.heads_lanes = False
+m.heads_at_peaks = not a.dense_heads
+m.heads_lanes = m.heads_at_peaks   # at the peaks the decoder's NMS + top-K runs in line on the one stream (its lane stays empty)
 m = bench.synthetic_weights(m).to(dev).eval()
 images, pc_dep, calib = bench.make_inputs(a.batch, H, W, dev, 1000)
 with torch.no_grad():
