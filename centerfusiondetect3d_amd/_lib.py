@@ -194,6 +194,8 @@ SYMBOLS = {
     "cf_head_train_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
     "cf_head_bwd_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
     "cf_head_bwd_chunk_px": (_i, [_i, _i, _i, _i]),
+    "cf_head_backward_dx": (_i, [C.POINTER(HeadTrainArgs), _f, _i, _f, _i, _f]),
+    "cf_head_bwd_dx_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
     "cf_upsample_dw": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _f]),
     "cf_maxpool2x2": (_i, [_f, _f, _i, _i, _i, _i, _f]),
     "cf_nchw_to_nhwc4": (_i, [_f, _f, _i, _i, _i, _i, _f]),

@@ -11,7 +11,11 @@
 // Products on the exact fp32-input MFMA (v_mfma_f32_32x32x2_f32), fp32 accumulation; the small output layer on the VALU (fmaf).
 // Weight / bias gradients are summed over pixel slabs with float atomics, and the compaction orders the list with an atomic
 // counter: gradients can differ in their last bits from run to run.  The forward has neither and is bitwise reproducible.
-// dX is not produced (frozen trunk).
+//
+// dX is produced on request only (cf_head_backward_dx; cf_head_backward serves a frozen trunk and launches nothing for it): at the
+// end of each chunk the masked gradient of the first layer's pre-activation is multiplied with the 3x3 weights and scattered from
+// the list to the nine neighbours of each pixel with float atomics (head_dgrad_kernel), into maps zeroed once per call - like
+// gw / gb, gx / gx2 can differ in their last bits from run to run.
 #include "cf_common.h"
 
 namespace {
@@ -259,6 +263,119 @@ __global__ __launch_bounds__(256) void head_wk_kernel(const float* __restrict__ 
   }
 }
 
+struct HDgrad {
+  const float* g;      // chunk-local masked gradient of the first layer's pre-activation [chunk][HID]
+  const float* wd;     // [9][HID][K]: the first layer's weights, K-major over the outputs o
+  float* gx;           // (B,h,w,gxs): columns c < cx; float atomics; null: skipped
+  float* gx2;          // (B,h,w,gx2s): columns cx <= c < K; null: skipped
+  const int* idx;
+  const int* count;
+  int M, begin, chunk, K, cx, gxs, gx2s, h, w;
+};
+
+// One wave = 32 list positions x 32 input channels, once per tap: D[position][c] = sum_o g[position][o] wd[tap][o][c], two o per
+// MFMA, then added at the pixel the tap points to.  The accumulator's lane index is the channel: one register is two 128-byte
+// segments in two pixel rows.  Whether a tap's pixel exists is decided from (b, y, x) - a neighbour outside the image, or in the
+// next one, receives nothing - and only then does the linear index move.  The 16 adds of a tap go out together behind its 128
+// MFMAs: an add stays counted among the outstanding memory operations for thousands of cycles and every load issued behind it
+// waits for it, so adds spread through the k loop (one per 8 MFMAs, measured: 2,970 cycles per k step) stall each step, a burst
+// stalls once per tap.  The operands of k step i + 1 are loaded ahead of the MFMAs of step i.
+struct DgradOps {
+  f32x4 a4[2];
+  float bw[2][4];
+};
+
+// half 0 holds outputs 16 i .. + 3 (and + 8), half 1 the four behind them (arow / wcol carry the half's offset)
+__device__ __forceinline__ void dgrad_load(DgradOps& t, const float* arow, const float* wcol, int K, int i) {
+#pragma unroll
+  for (int v = 0; v < 2; ++v) {
+    const int kb = 16 * i + 8 * v;
+    t.a4[v] = *reinterpret_cast<const f32x4*>(arow + kb);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) t.bw[v][s] = wcol[(size_t)(kb + s) * K];
+  }
+}
+
+__device__ __forceinline__ void dgrad_mfma(f32x16& acc, const DgradOps& t, bool live) {
+#pragma unroll
+  for (int v = 0; v < 2; ++v)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(live ? t.a4[v][s] : 0.0f, t.bw[v][s], acc, 0, 0, 0);
+}
+
+__global__ __launch_bounds__(64) void head_dgrad_kernel(const HDgrad p) {
+  const int lane = threadIdx.x, half = lane >> 5, cl = lane & 31;
+  const int end = list_end(p.count, p.M, p.begin, p.chunk);
+  const int K = p.K;
+  const int c = blockIdx.y * 32 + cl;
+  const int cc = c < K ? c : K - 1;
+  float* dst = nullptr;              // this lane's column of pixel 0 (null: nothing is added)
+  int ds = 0;
+  if (c < p.cx) {
+    if (p.gx) { dst = p.gx + c; ds = p.gxs; }
+  } else if (c < K) {
+    if (p.gx2) { dst = p.gx2 + (c - p.cx); ds = p.gx2s; }
+  }
+  const int hw = p.h * p.w;
+  for (int q0 = p.begin + blockIdx.x * GEMM_PX; q0 < end; q0 += gridDim.x * GEMM_PX) {
+    // the 16 positions of this lane's accumulator registers: pixel index and the taps whose pixel lies inside the image
+    int pix[16], inside[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int qq = q0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+      const bool on = qq < end && dst;
+      const int pv = p.idx[qq < end ? qq : end - 1];
+      const int pb = pv / hw, rem = pv - pb * hw;
+      const int py = rem / p.w, px = rem - py * p.w;
+      int m = 0;
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        const int yy = py + tap / 3 - 1, xx = px + tap % 3 - 1;
+        m |= (yy >= 0 && yy < p.h && xx >= 0 && xx < p.w) ? 1 << tap : 0;
+      }
+      pix[r] = pv;
+      inside[r] = on ? m : 0;
+    }
+    const int q = q0 + cl;
+    const bool live = q < end;
+    const float* arow = p.g + (size_t)((live ? q : end - 1) - p.begin) * HID + 4 * half;
+#pragma unroll 1
+    for (int tap = 0; tap < 9; ++tap) {
+      const int poff = (tap / 3 - 1) * p.w + tap % 3 - 1;
+      const float* wcol = p.wd + ((size_t)tap * HID + 4 * half) * K + cc;
+      f32x16 acc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+      DgradOps even, odd;
+      dgrad_load(even, arow, wcol, K, 0);
+#pragma unroll 1
+      for (int i = 0; i < HID / 16; i += 2) {
+        dgrad_load(odd, arow, wcol, K, i + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        dgrad_mfma(acc, even, live);
+        __builtin_amdgcn_sched_barrier(0);
+        dgrad_load(even, arow, wcol, K, (i + 2) & (HID / 16 - 1));     // (the last step's is not used: the address stays inside)
+        __builtin_amdgcn_sched_barrier(0);
+        dgrad_mfma(acc, odd, live);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (inside[r] >> tap & 1) atomicAdd(dst + (size_t)(pix[r] + poff) * ds, acc[r]);
+    }
+  }
+}
+
+// dst[(tap * HID + o) * K + c] = src[(o * K + c) * 9 + tap]: the raw (256, K, 3, 3) weight, K-major over o
+__global__ __launch_bounds__(256) void head_wd_kernel(const float* __restrict__ src, float* __restrict__ dst, int K) {
+  const int n = 9 * K * HID;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const int c = i % K, to = i / K;
+    const int o = to & (HID - 1), tap = to >> 8;
+    dst[i] = src[((size_t)o * K + c) * 9 + tap];
+  }
+}
+
 // the list of pixels where any channel of gy (NCHW) is non-zero; *count zeroed by the caller
 __global__ __launch_bounds__(256) void head_compact_kernel(const float* __restrict__ gy, int M, int hw, int n_out,
                                                            int* __restrict__ idx, int* __restrict__ count) {
@@ -365,7 +482,7 @@ size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 struct Layout {
   int chunk;
-  size_t wk1, wt, count, idx, bufs, total;   // byte offsets
+  size_t wk1, wt, count, idx, bufs, wd, total;   // byte offsets
 };
 
 int resolve_chunk(long M, int chunk_px) {
@@ -375,7 +492,7 @@ int resolve_chunk(long M, int chunk_px) {
   return (int)c;
 }
 
-Layout layout(int B, int h, int w, int Cin, int n_hidden, int chunk_px, bool backward) {
+Layout layout(int B, int h, int w, int Cin, int n_hidden, int chunk_px, bool backward, bool dx = false) {
   Layout L{};
   const long M = (long)B * h * w;
   L.chunk = resolve_chunk(M, chunk_px);
@@ -385,11 +502,19 @@ Layout layout(int B, int h, int w, int Cin, int n_hidden, int chunk_px, bool bac
   L.count = at; at += 16;
   L.idx = at; at += backward ? align16((size_t)M * 4) : 0;
   L.bufs = at; at += (size_t)(backward ? n_hidden + 3 : 2) * L.chunk * HID * 4;
+  L.wd = at; at += dx ? align16((size_t)9 * Cin * HID * 4) : 0;     // (behind everything cf_head_backward lays out)
   L.total = at;
   return L;
 }
 
-int head_check(const cf_head_train_args* a, const char* who, bool backward) {
+// where cf_head_backward_dx leaves the sources' gradient
+struct DxOut {
+  float* gx;
+  float* gx2;
+  int gxs, gx2s;
+};
+
+int head_check(const cf_head_train_args* a, const char* who, bool backward, const DxOut* dx = nullptr) {
   CF_REQUIRE(a != nullptr, "%s: null args", who);
   CF_REQUIRE(a->B > 0 && a->h > 0 && a->w > 0, "%s: bad geometry", who);
   CF_REQUIRE(a->n_hidden >= 0 && a->n_hidden <= CF_HEAD_TRAIN_MAX_HIDDEN, "%s: n_hidden=%d outside 0..%d", who, a->n_hidden,
@@ -401,13 +526,21 @@ int head_check(const cf_head_train_args* a, const char* who, bool backward) {
   CF_REQUIRE(a->c_x + a->c_x2 <= 512, "%s: Cin=%d above 512", who, a->c_x + a->c_x2);
   const long M = (long)a->B * a->h * a->w;
   CF_REQUIRE(M * (a->x_stride > HID ? a->x_stride : HID) < (1L << 31) && M * 16 < (1L << 31), "%s: tensor too large", who);
+  if (dx) {
+    CF_REQUIRE(dx->gx || dx->gx2, "%s: gx and gx2 are both null (cf_head_backward is the call without a source gradient)", who);
+    CF_REQUIRE(!dx->gx || dx->gxs >= a->c_x, "%s: gx_stride=%d below c_x=%d", who, dx->gxs, a->c_x);
+    CF_REQUIRE(!dx->gx2 || a->x2, "%s: gx2 without x2", who);
+    CF_REQUIRE(!dx->gx2 || dx->gx2s >= a->c_x2, "%s: gx2_stride=%d below c_x2=%d", who, dx->gx2s, a->c_x2);
+    CF_REQUIRE(!dx->gx || M * dx->gxs < (1L << 31), "%s: gx too large", who);
+    CF_REQUIRE(!dx->gx2 || M * dx->gx2s < (1L << 31), "%s: gx2 too large", who);
+  }
   CF_REQUIRE(a->chunk_px >= 0 && a->chunk_px % 64 == 0, "%s: chunk_px=%d must be a multiple of 64 (0: the default)", who, a->chunk_px);
   for (int l = 0; l < a->n_hidden + 2; ++l) {
     CF_REQUIRE(a->weight[l] && a->bias[l], "%s: null weight / bias of layer %d", who, l);
     if (backward) CF_REQUIRE(a->gw[l] && a->gb[l], "%s: null gw / gb of layer %d", who, l);
   }
   CF_REQUIRE(backward ? a->gy != nullptr : a->y != nullptr, "%s: null %s", who, backward ? "gy" : "y");
-  const Layout L = layout(a->B, a->h, a->w, a->c_x + a->c_x2, a->n_hidden, a->chunk_px, backward);
+  const Layout L = layout(a->B, a->h, a->w, a->c_x + a->c_x2, a->n_hidden, a->chunk_px, backward, dx != nullptr);
   CF_REQUIRE(a->workspace && a->workspace_bytes >= L.total, "%s: workspace of %zu bytes is smaller than the %zu needed", who,
              a->workspace_bytes, L.total);
   CF_REQUIRE((reinterpret_cast<uintptr_t>(a->workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
@@ -481,6 +614,11 @@ extern "C" size_t cf_head_bwd_workspace_bytes(int B, int h, int w, int Cin, int 
   return layout(B, h, w, Cin, n_hidden, chunk_px, true).total;
 }
 
+extern "C" size_t cf_head_bwd_dx_workspace_bytes(int B, int h, int w, int Cin, int n_hidden, int chunk_px) {
+  if (B <= 0 || h <= 0 || w <= 0 || Cin <= 0 || n_hidden < 0 || chunk_px < 0) return 0;
+  return layout(B, h, w, Cin, n_hidden, chunk_px, true, true).total;
+}
+
 extern "C" int cf_head_bwd_chunk_px(int B, int h, int w, int chunk_px) {
   if (B <= 0 || h <= 0 || w <= 0 || chunk_px < 0) return 0;
   return resolve_chunk((long)B * h * w, chunk_px);
@@ -505,11 +643,14 @@ extern "C" int cf_head_train_forward(const cf_head_train_args* a, void* stream) 
   return cf_check_launch("cf_head_train_forward");
 }
 
-extern "C" int cf_head_backward(const cf_head_train_args* a, void* stream) {
-  if (int e = head_check(a, "cf_head_backward", true)) return e;
+namespace {
+
+// cf_head_backward (dx null) and cf_head_backward_dx: the same launches, and behind each chunk's the scatter of dX
+int head_backward(const cf_head_train_args* a, const char* who, const DxOut* dx, void* stream) {
+  if (int e = head_check(a, who, true, dx)) return e;
   hipStream_t st = (hipStream_t)stream;
   const int Cin = a->c_x + a->c_x2, nh = a->n_hidden;
-  const Layout L = layout(a->B, a->h, a->w, Cin, nh, a->chunk_px, true);
+  const Layout L = layout(a->B, a->h, a->w, Cin, nh, a->chunk_px, true, dx != nullptr);
   char* ws = static_cast<char*>(a->workspace);
   int* count = reinterpret_cast<int*>(ws + L.count);
   int* idx = reinterpret_cast<int*>(ws + L.idx);
@@ -518,7 +659,7 @@ extern "C" int cf_head_backward(const cf_head_train_args* a, void* stream) {
   for (int i = 0; i < nh + 3; ++i) bufs[i] = base + (size_t)i * L.chunk * HID;
   const long M = (long)a->B * a->h * a->w;
   const int hw = a->h * a->w;
-  if (hipMemsetAsync(count, 0, 16, st) != hipSuccess) return cf_check_launch("cf_head_backward");
+  if (hipMemsetAsync(count, 0, 16, st) != hipSuccess) return cf_check_launch(who);
   (void)hipMemsetAsync(a->gw[0], 0, (size_t)HID * Cin * 9 * 4, st);
   for (int l = 1; l <= nh; ++l) (void)hipMemsetAsync(a->gw[l], 0, (size_t)HID * HID * 4, st);
   (void)hipMemsetAsync(a->gw[nh + 1], 0, (size_t)a->n_out * HID * 4, st);
@@ -526,6 +667,13 @@ extern "C" int cf_head_backward(const cf_head_train_args* a, void* stream) {
   (void)hipMemsetAsync(a->gb[nh + 1], 0, (size_t)a->n_out * 4, st);
   hipLaunchKernelGGL(head_compact_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, a->gy, (int)M, hw, a->n_out, idx, count);
   launch_wk(a, L, st);
+  if (dx) {
+    // zeroed once, padding channels included: neighbouring pixels of different chunks add into the same rows
+    if (dx->gx) (void)hipMemsetAsync(dx->gx, 0, (size_t)M * dx->gxs * 4, st);
+    if (dx->gx2) (void)hipMemsetAsync(dx->gx2, 0, (size_t)M * dx->gx2s * 4, st);
+    hipLaunchKernelGGL(head_wd_kernel, dim3(blocks_for(9L * Cin * HID, 1024)), dim3(256), 0, st, a->weight[0],
+                       reinterpret_cast<float*>(ws + L.wd), Cin);
+  }
   const int slabs = (L.chunk + SLAB_PX - 1) / SLAB_PX;
   const int tiles = (L.chunk + GEMM_PX - 1) / GEMM_PX;
   for (long begin = 0; begin < M; begin += L.chunk) {
@@ -557,6 +705,24 @@ extern "C" int cf_head_backward(const cf_head_train_args* a, void* stream) {
     w1.idx = idx; w1.count = count; w1.M = (int)M; w1.begin = (int)begin; w1.chunk = L.chunk; w1.K = Cin;
     w1.ostride = Cin * 9; w1.cstride = 9;
     hipLaunchKernelGGL(head_wgrad_kernel<9>, dim3((unsigned)slabs, (unsigned)(9 * ((Cin + 31) / 32)), 2), dim3(64), 0, st, w1);
+    if (dx) {
+      HDgrad d{};
+      d.g = g; d.wd = reinterpret_cast<const float*>(ws + L.wd); d.gx = dx->gx; d.gx2 = dx->gx2;
+      d.idx = idx; d.count = count; d.M = (int)M; d.begin = (int)begin; d.chunk = L.chunk; d.K = Cin; d.cx = a->c_x;
+      d.gxs = dx->gxs; d.gx2s = dx->gx2s; d.h = a->h; d.w = a->w;
+      hipLaunchKernelGGL(head_dgrad_kernel, dim3((unsigned)(tiles < 4096 ? tiles : 4096), (unsigned)((Cin + 31) / 32)), dim3(64), 0, st, d);
+    }
   }
-  return cf_check_launch("cf_head_backward");
+  return cf_check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int cf_head_backward(const cf_head_train_args* a, void* stream) {
+  return head_backward(a, "cf_head_backward", nullptr, stream);
+}
+
+extern "C" int cf_head_backward_dx(const cf_head_train_args* a, float* gx, int gx_stride, float* gx2, int gx2_stride, void* stream) {
+  const DxOut dx{gx, gx2, gx_stride, gx2_stride};
+  return head_backward(a, "cf_head_backward_dx", &dx, stream);
 }

@@ -5,7 +5,8 @@ Drop-in boundary: same factory (`getModel(config)`, model/mod
 base_model.py:30-53 + detectHeads.py:32-163), same call
 `model(images, pc_hm=None, pc_dep=None, calib=None) -> [dict]` (base_model.py:67-106) with the
 same keys, order, shapes and the `pc_hm_in` view of the caller's `pc_dep`
-(detectHeads.py:172).  Eval mode, and one training mode: the heads on a frozen trunk (MODEL.FREEZE_BACKBONE, `_forward_train`).
+(detectHeads.py:172).  Eval mode, and one training mode: the heads on a frozen trunk (MODEL.FREEZE_BACKBONE, `_forward_train`); `forward_trunk` /
+`forward_heads` are its two halves, the second differentiable in a caller's feature map.
 
 Nothing else is shared with the reference's design.  The module is a parameter tree plus an
 *execution plan*: at first call for a given (B,H,W) it lays out every intermediate NHWC buffer in
@@ -723,14 +724,7 @@ class DLASeg(nn.Module):
                 cur.wait_stream(s)
             return feat
 
-    def _forward_train(self, x, pc_hm, pc_dep, calib):
-        """model.train() with MODEL.FREEZE_BACKBONE: the reference's training forward (base_model.py:83-106, detectHeads.py:117-191)
-        with the trunk frozen.  The trunk runs through the eval plan under no_grad; every head runs through `ops.head_stack` on the
-        module's own parameters, so `loss.backward()` leaves a gradient on each `detectHead_0.*` parameter and on nothing else.
-        Middle fusion: the caller's `pc_hm` (B,3,H/4,W/4) - the dataset's association map - feeds the secondary heads; no frustum
-        association runs and nothing is normalised in place.  Early fusion: `pc_hm` is the map the six-channel stem reads.
-        Deviation from the reference: the frozen trunk always uses the folded running statistics of its BatchNorm layers (the
-        reference leaves dla_up / ida_up - and, without MODEL.NORM_EVAL, base - in batch-statistics mode)."""
+    def _check_train_images(self, x):
         if self.use_graph:
             raise NotImplementedError("training mode: model.use_graph is not supported (autograd does not record through a captured "
                                       "graph); set model.use_graph = False")
@@ -738,61 +732,128 @@ class DLASeg(nn.Module):
             raise _lib.CfHipError("DLASeg.forward needs device tensors: the HIP path has no CPU fallback")
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
             raise ValueError(f"images must be (B,3,H,W) with H,W multiples of 32, got {tuple(x.shape)}")
+
+    def _check_train_radar(self, B, h4, w4, pc_hm, pc_dep):
+        """the radar arguments of a training forward on a (B, h4, w4) feature map -> pc_hm detached and contiguous (or None)"""
+        if not self.isRadarEnabled:
+            return pc_hm
+        if pc_hm is None:
+            raise ValueError("radar model in training mode: pc_hm (the dataset's radar map) is required - no frustum "
+                             "association runs in training (detectHeads.py:176-181)")
+        if tuple(pc_hm.shape) != (B, 3, h4, w4) or pc_hm.dtype != torch.float32:
+            raise ValueError(f"pc_hm must be float32 {(B, 3, h4, w4)}, got {pc_hm.dtype} {tuple(pc_hm.shape)}")
+        if not self.isEarly and (pc_dep is None or tuple(pc_dep.shape) != (B, 3, h4, w4)):
+            raise ValueError(f"radar model: pc_dep must be {(B, 3, h4, w4)}")
+        return pc_hm.detach().contiguous()
+
+    def _forward_train(self, x, pc_hm, pc_dep, calib):
+        """model.train() with MODEL.FREEZE_BACKBONE: the reference's training forward (base_model.py:83-106, detectHeads.py:117-191)
+        with the trunk frozen.  The trunk runs through the eval plan under no_grad; every head runs through `ops.head_stack` on the
+        module's own parameters, so `loss.backward()` leaves a gradient on each `detectHead_0.*` parameter and on nothing else.
+        Middle fusion: the caller's `pc_hm` (B,3,H/4,W/4) - the dataset's association map - feeds the secondary heads; no frustum
+        association runs and nothing is normalised in place.  Early fusion: `pc_hm` is the map the six-channel stem reads.
+        Deviation from the reference: the frozen trunk always uses the folded running statistics of its BatchNorm layers (the
+        reference leaves dla_up / ida_up - and, without MODEL.NORM_EVAL, base - in batch-statistics mode).
+        It is `forward_heads` on `_train_trunk`'s map."""
+        self._check_train_images(x)
         B, _, H, W = x.shape
         dev = x.device
-        h4, w4 = H // 4, W // 4
         x = x.detach().float().contiguous()
-        middle = self.isRadarEnabled and not self.isEarly
-        if self.isRadarEnabled:
-            if pc_hm is None:
-                raise ValueError("radar model in training mode: pc_hm (the dataset's radar map) is required - no frustum "
-                                 "association runs in training (detectHeads.py:176-181)")
-            if tuple(pc_hm.shape) != (B, 3, h4, w4) or pc_hm.dtype != torch.float32:
-                raise ValueError(f"pc_hm must be float32 {(B, 3, h4, w4)}, got {pc_hm.dtype} {tuple(pc_hm.shape)}")
-            if middle and (pc_dep is None or tuple(pc_dep.shape) != (B, 3, h4, w4)):
-                raise ValueError(f"radar model: pc_dep must be {(B, 3, h4, w4)}")
-            pc_hm = pc_hm.detach().contiguous()
-        heads, secondary = self.config.heads, (SECONDARY_HEADS if middle else [])
+        pc_hm = self._check_train_radar(B, H // 4, W // 4, pc_hm, pc_dep)
         with self._lock, torch.cuda.device(dev):
             if self._packed is None:
                 self._prepare(dev)
             sid = torch.cuda.current_stream(dev).cuda_stream
             # (a copy: autograd keeps the map until backward, the plan's buffer is overwritten by the next forward)
             feat = self._train_trunk(x, pc_hm if self.isEarly else None, B, H, W, dev, sid).clone()
-            self._stale = True
-            y = {}
+            return self._heads_train(feat, False, pc_hm, pc_dep, calib)
 
-            def run(h, x2n):
-                ws, bs = self._head_params(h)
-                final = "heatmap" if h == "heatmap" else ("depth" if h in ("depth", "depth2") else None)
-                return ops.head_stack_nhwc(feat, 64, x2n, 0 if x2n is None else 3, ws, bs, final=final)
+    def forward_trunk(self, images, pc_hm=None):
+        """The frozen trunk alone: images (B,3,H,W) -> the (B,64,H/4,W/4) NCHW feature map the heads read, under no_grad, a fresh
+        tensor (`forward_heads(forward_trunk(images), ...)` is the training forward).  Early fusion: `pc_hm` (B,3,H/4,W/4) is the
+        radar map the six-channel stem reads.  Works in either mode and whatever MODEL.FREEZE_BACKBONE says: the trunk always
+        runs through the eval plan (split-fp16, BatchNorm folded with the running statistics) and is not differentiable."""
+        self._check_train_images(images)
+        B, _, H, W = images.shape
+        dev = images.device
+        x = images.detach().float().contiguous()
+        pc = None
+        if self.isEarly:
+            pc = self._check_train_radar(B, H // 4, W // 4, pc_hm, None)
+        with self._lock, torch.cuda.device(dev):
+            if self._packed is None:
+                self._prepare(dev)
+            sid = torch.cuda.current_stream(dev).cuda_stream
+            with torch.no_grad():
+                return ops.nhwc_to_nchw(self._train_trunk(x, pc, B, H, W, dev, sid))
 
-            for h in heads:
-                if h in secondary:
-                    continue
-                r = run(h, None)
-                y[h] = r[0] if isinstance(r, tuple) else r
-                if h == "depth":
-                    depth_raw = r[1]
-            if "depth" in heads:
-                y["depthMap"] = depth_raw
-            y["calib"] = calib
-            if middle:
-                y["pc_hm_in"] = pc_dep[:, :1]
-                y["pc_hm"] = pc_hm[:, 0, :, :].unsqueeze(1)
+    def forward_heads(self, feat, pc_hm=None, pc_dep=None, calib=None):
+        """The reference's `detectHead_0(imgFeatures, pc_hm, pc_dep, calib)` in training mode on a caller's feature map: `feat`
+        (B,64,h,w) fp32 on the device - `forward_trunk`'s, or the output of a trunk / neck of the caller's own.  Same dict, keys,
+        order and argument checks as the training forward.  Differentiable in every `detectHead_0.*` parameter and, when `feat`
+        requires grad, in `feat` (`ops.head_stack(..., input_grad=True)`: the eleven heads' gradients are summed by autograd);
+        the radar map is never differentiated.  Training mode only, whatever MODEL.FREEZE_BACKBONE says; marks the packed head
+        weights stale as a training forward does."""
+        if not self.training:
+            raise NotImplementedError("forward_heads is the training forward of the heads: call model.train() first (the eval "
+                                      "forward runs the packed heads at the peaks, model(images, ...))")
+        if self.use_graph:
+            raise NotImplementedError("training mode: model.use_graph is not supported (autograd does not record through a captured "
+                                      "graph); set model.use_graph = False")
+        if not torch.is_tensor(feat) or not feat.is_cuda:
+            raise _lib.CfHipError("DLASeg.forward_heads needs device tensors: the HIP path has no CPU fallback")
+        if feat.dim() != 4 or feat.shape[1] != 64 or feat.dtype != torch.float32:
+            raise ValueError(f"feat must be float32 (B,64,h,w), got {feat.dtype} {tuple(feat.shape)}")
+        B, _, h4, w4 = feat.shape
+        pc_hm = self._check_train_radar(B, h4, w4, pc_hm, pc_dep)
+        with self._lock, torch.cuda.device(feat.device):
+            grad = torch.is_grad_enabled() and feat.requires_grad
+            if grad:
+                featn = ops._NchwToNhwcFn.apply(feat)
+            else:
                 with torch.no_grad():
-                    pcn = ops.nchw_to_nhwc(pc_hm)
-                for h in secondary:
-                    if h not in heads:
-                        continue
-                    r = run(h, pcn)
-                    y[h] = r[1] if h == "depth2" else r          # (depth2: the raw map until depthMap has taken it)
-                    if h == "depth2":
-                        act = r[0]
-                y["pc_hm_out"] = pc_hm[:, :1]
-                if "depth2" in heads:
-                    y["depthMap"] = y["depth2"]
-                    y["depth2"] = act
+                    featn = ops.nchw_to_nhwc(feat.contiguous())
+            return self._heads_train(featn, grad, pc_hm, pc_dep, calib)
+
+    def _heads_train(self, feat, input_grad, pc_hm, pc_dep, calib):
+        """every head through `ops.head_stack_nhwc` on the NHWC map `feat` (B,h,w,64) and the module's own parameters; the
+        arguments are checked (`_check_train_radar`), the lock is held"""
+        middle = self.isRadarEnabled and not self.isEarly
+        heads, secondary = self.config.heads, (SECONDARY_HEADS if middle else [])
+        self._stale = True
+        y = {}
+
+        def run(h, x2n):
+            ws, bs = self._head_params(h)
+            final = "heatmap" if h == "heatmap" else ("depth" if h in ("depth", "depth2") else None)
+            return ops.head_stack_nhwc(feat, 64, x2n, 0 if x2n is None else 3, ws, bs, final=final, input_grad=input_grad)
+
+        for h in heads:
+            if h in secondary:
+                continue
+            r = run(h, None)
+            y[h] = r[0] if isinstance(r, tuple) else r
+            if h == "depth":
+                depth_raw = r[1]
+        if "depth" in heads:
+            y["depthMap"] = depth_raw
+        y["calib"] = calib
+        if middle:
+            y["pc_hm_in"] = pc_dep[:, :1]
+            y["pc_hm"] = pc_hm[:, 0, :, :].unsqueeze(1)
+            with torch.no_grad():
+                pcn = ops.nchw_to_nhwc(pc_hm)
+            for h in secondary:
+                if h not in heads:
+                    continue
+                r = run(h, pcn)
+                y[h] = r[1] if h == "depth2" else r          # (depth2: the raw map until depthMap has taken it)
+                if h == "depth2":
+                    act = r[0]
+            y["pc_hm_out"] = pc_hm[:, :1]
+            if "depth2" in heads:
+                y["depthMap"] = y["depth2"]
+                y["depth2"] = act
         return [y]
 
     def _forward_eager(self, x, pc_dep, calib, B, H, W, dev, sid, store=None):

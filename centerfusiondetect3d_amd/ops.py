@@ -786,7 +786,7 @@ def generic_loss(heat, heat_gt, centers, wh, mask, cls, heads, heat_weight=1.0, 
         return _loss_run_forward(spec, tensors)[:3]
 
 
-# ---- one detection head under autograd (cf_head_train_forward / cf_head_backward) ----
+# ---- one detection head under autograd (cf_head_train_forward / cf_head_backward / cf_head_backward_dx) ----
 HEAD_HIDDEN = 256          # width of every hidden map the training kernels implement
 HEAD_MAX_OUT = 16          # outputs of a head's last layer
 HEAD_MAX_HIDDEN = _lib.CF_HEAD_TRAIN_MAX_HIDDEN   # 1x1 hidden layers behind the 3x3
@@ -849,10 +849,11 @@ def _workspace(a, nbytes):
 
 class _HeadStackFn(torch.autograd.Function):
     """`head_stack` under autograd: cf_head_train_forward; the NHWC sources and the raw weights saved (no hidden map is);
-    backward on cf_head_backward: every layer's weight and bias gradient, none for the sources."""
+    backward on cf_head_backward: every layer's weight and bias gradient, none for the sources - or, with `input_grad` and a
+    source that autograd asks for, on cf_head_backward_dx: also that source's gradient, in its own (B,h,w,S) shape."""
 
     @staticmethod
-    def forward(ctx, xn, x2n, c_x, c_x2, chunk_px, n_layers, *params):
+    def forward(ctx, xn, x2n, c_x, c_x2, chunk_px, n_layers, input_grad, *params):
         weights = [p.detach().contiguous() for p in params[:n_layers]]
         biases = [p.detach().contiguous() for p in params[n_layers:]]
         B, h, w = xn.shape[:3]
@@ -862,14 +863,14 @@ class _HeadStackFn(torch.autograd.Function):
             a.y = y.data_ptr()
             ws = _workspace(a, _lib.load().cf_head_train_workspace_bytes(B, h, w, c_x + c_x2, a.n_hidden, int(chunk_px)))
             _lib.check(_lib.load().cf_head_train_forward(C.byref(a), _lib.stream_ptr()), "cf_head_train_forward")
-        ctx.meta = (c_x, c_x2, int(chunk_px), n_layers, x2n is not None)
+        ctx.meta = (c_x, c_x2, int(chunk_px), n_layers, x2n is not None, bool(input_grad))
         ctx.save_for_backward(xn, *([x2n] if x2n is not None else []), *weights, *biases)
         return y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        c_x, c_x2, chunk_px, n, has2 = ctx.meta
+        c_x, c_x2, chunk_px, n, has2, input_grad = ctx.meta
         saved = list(ctx.saved_tensors)
         xn = saved.pop(0)
         x2n = saved.pop(0) if has2 else None
@@ -883,11 +884,35 @@ class _HeadStackFn(torch.autograd.Function):
             for l in range(n):
                 a.gw[l], a.gb[l] = gws[l].data_ptr(), gbs[l].data_ptr()
             a.gy = gy.data_ptr()
-            ws = _workspace(a, _lib.load().cf_head_bwd_workspace_bytes(B, h, w, c_x + c_x2, a.n_hidden, chunk_px))
-            _lib.check(_lib.load().cf_head_backward(C.byref(a), _lib.stream_ptr()), "cf_head_backward")
-        need = ctx.needs_input_grad[6:]
+            want = input_grad and ctx.needs_input_grad[0], input_grad and has2 and ctx.needs_input_grad[1]
+            gx = torch.empty_like(xn) if want[0] else None
+            gx2 = torch.empty_like(x2n) if want[1] else None
+            if gx is None and gx2 is None:
+                ws = _workspace(a, _lib.load().cf_head_bwd_workspace_bytes(B, h, w, c_x + c_x2, a.n_hidden, chunk_px))
+                _lib.check(_lib.load().cf_head_backward(C.byref(a), _lib.stream_ptr()), "cf_head_backward")
+            else:
+                ws = _workspace(a, _lib.load().cf_head_bwd_dx_workspace_bytes(B, h, w, c_x + c_x2, a.n_hidden, chunk_px))
+                _lib.check(_lib.load().cf_head_backward_dx(C.byref(a), _lib.ptr(gx), xn.shape[-1], _lib.ptr(gx2),
+                                                           0 if x2n is None else x2n.shape[-1], _lib.stream_ptr()),
+                           "cf_head_backward_dx")
+        need = ctx.needs_input_grad[7:]
         grads = [g if nd else None for g, nd in zip(gws + gbs, need)]
-        return (None, None, None, None, None, None, *grads)
+        return (gx, gx2, None, None, None, None, None, *grads)
+
+
+class _NchwToNhwcFn(torch.autograd.Function):
+    """`head_stack`'s layout conversion under autograd: cf_nchw_to_nhwc forward, cf_nhwc_to_nchw backward."""
+
+    @staticmethod
+    def forward(ctx, x):
+        with torch.cuda.device(x.device):
+            return nchw_to_nhwc(x.detach().contiguous())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        with torch.cuda.device(g.device):
+            return nhwc_to_nchw(g.detach().contiguous())
 
 
 def head_final(y, final):
@@ -900,15 +925,17 @@ def head_final(y, final):
     return y
 
 
-def head_stack_nhwc(xn, c_x, x2n, c_x2, weights, biases, final=None, chunk_px=0):
+def head_stack_nhwc(xn, c_x, x2n, c_x2, weights, biases, final=None, chunk_px=0, input_grad=False):
     """`head_stack` on sources that are already NHWC: xn (B,h,w,S) whose first c_x channels are read, x2n (B,h,w,S2) / c_x2 the
-    optional second source (DLASeg's training forward: the trunk's feature map and the radar map, never concatenated)."""
+    optional second source (DLASeg's training forward: the trunk's feature map and the radar map, never concatenated).
+    `input_grad=True`: a source that requires grad receives its gradient in its own (B,h,w,S) shape - the channels behind
+    c_x / c_x2 exactly zero; without it the sources receive none."""
     weights, biases = list(weights), list(biases)
-    y = _HeadStackFn.apply(xn, x2n, int(c_x), int(c_x2), int(chunk_px), len(weights), *weights, *biases)
+    y = _HeadStackFn.apply(xn, x2n, int(c_x), int(c_x2), int(chunk_px), len(weights), bool(input_grad), *weights, *biases)
     return y if final is None else (head_final(y, final), y)
 
 
-def head_stack(x, weights, biases, final=None, x2=None, chunk_px=0):
+def head_stack(x, weights, biases, final=None, x2=None, chunk_px=0, input_grad=False):
     """One detection head of the reference (detectHeads.py:59-98) under autograd, on HIP kernels in both directions:
     conv3x3(Cin -> 256) + bias -> ReLU -> [conv1x1(256 -> 256) + bias -> ReLU] x n -> conv1x1(256 -> Cout) + bias, n = 0 .. 2,
     Cout = 1 .. 16.  `x` (B,Cin,h,w) fp32 on the device; `x2` (B,C2,h,w): an optional second source whose channels follow x's
@@ -916,8 +943,11 @@ def head_stack(x, weights, biases, final=None, x2=None, chunk_px=0):
     layer order ((256,Cin+C2,3,3), (256,256,1,1) x n, (Cout,256,1,1)).  -> the raw map (B,Cout,h,w) when `final` is None;
     (activated map, raw map) for final = "heatmap" / "depth" (`head_final`: torch elementwise ops on top of the operator).
 
-    Differentiable once in every weight and bias; NOT in x / x2 (a frozen trunk never asks; a source that requires grad raises
-    NotImplementedError).  The forward keeps no hidden map: the backward compacts the pixels with a non-zero output gradient on
+    Differentiable once in every weight and bias; in x / x2 only with `input_grad=True` (the default serves a frozen trunk, which
+    never asks: a source that requires grad then raises NotImplementedError).  With it, each source that requires grad receives
+    its gradient: the masked gradient of the first layer is multiplied with the 3x3 weights and scattered to the nine neighbours
+    of every active pixel (cf_head_backward_dx, one more launch per list chunk); when no source asks, the backward is the
+    default's.  The forward keeps no hidden map: the backward compacts the pixels with a non-zero output gradient on
     the device and recomputes the hidden maps for those alone, with the forward's own kernel - its cost follows the number of
     active pixels (plus one pass over dY and an empty launch per list chunk).  The forward is bitwise reproducible; the
     gradients are summed with float atomics and can differ in their last bits from run to run.  `chunk_px`: list positions per
@@ -926,14 +956,21 @@ def head_stack(x, weights, biases, final=None, x2=None, chunk_px=0):
     weights, biases = list(weights), list(biases)
     c_x, c_x2, _, _ = _head_check(x, x2, weights, biases, final)
     _need_cuda(x, x2, *weights, *biases)
-    if torch.is_grad_enabled() and (x.requires_grad or (x2 is not None and x2.requires_grad)):
-        raise NotImplementedError("head_stack: the gradient with respect to x is not implemented (frozen trunk only): detach it")
+    if not input_grad and torch.is_grad_enabled() and (x.requires_grad or (x2 is not None and x2.requires_grad)):
+        raise NotImplementedError("head_stack: the gradient with respect to x is off by default (frozen trunk only): detach it, "
+                                  "or pass input_grad=True")
     if int(chunk_px) < 0 or int(chunk_px) % 64:
         raise ValueError("head_stack: chunk_px must be a multiple of 64 (0: the default)")
-    with torch.no_grad(), torch.cuda.device(x.device):
-        xn = nchw_to_nhwc(x.contiguous())
-        x2n = None if x2 is None else nchw_to_nhwc(x2.contiguous())
-    return head_stack_nhwc(xn, c_x, x2n, c_x2, weights, biases, final, chunk_px)
+
+    def to_nhwc(t):
+        if input_grad and torch.is_grad_enabled() and t.requires_grad:
+            return _NchwToNhwcFn.apply(t)
+        with torch.no_grad(), torch.cuda.device(t.device):
+            return nchw_to_nhwc(t.contiguous())
+
+    xn = to_nhwc(x)
+    x2n = None if x2 is None else to_nhwc(x2)
+    return head_stack_nhwc(xn, c_x, x2n, c_x2, weights, biases, final, chunk_px, input_grad)
 
 
 def upsample_dw(x, weight_kkc, f, skip=None, out=None):

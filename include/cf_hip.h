@@ -699,7 +699,8 @@ size_t cf_loss_workspace_bytes(int B, int C, int h, int w);
  * Cin = c_x + c_x2: the channels of `x` followed by those of the optional second source `x2` (the radar channels of the secondary
  * heads: the concatenation is never materialised).  The hidden maps are not kept: both directions work through a list of pixels in
  * chunks of `chunk_px` rows held in the workspace, and the backward recomputes the hidden maps with the forward's own kernel (its
- * ReLU mask is the forward's bit for bit; ReLU'(0) = 0).  The gradient with respect to x is NOT produced. */
+ * ReLU mask is the forward's bit for bit; ReLU'(0) = 0).  The gradient with respect to x / x2 is produced by cf_head_backward_dx
+ * only; cf_head_backward serves a frozen trunk and does nothing for it. */
 #define CF_HEAD_TRAIN_MAX_HIDDEN 2
 typedef struct cf_head_train_args {
   const float* x;        /* NHWC [B][h][w][x_stride], channels 0 .. c_x-1 read                                     */
@@ -731,6 +732,16 @@ size_t cf_head_train_workspace_bytes(int B, int h, int w, int Cin, int n_hidden,
 size_t cf_head_bwd_workspace_bytes(int B, int h, int w, int Cin, int n_hidden, int chunk_px);
 /* the chunk length those calls use for this geometry and chunk_px (0: the default) */
 int cf_head_bwd_chunk_px(int B, int h, int w, int chunk_px);
+/* cf_head_backward - the same checks, launches, gw and gb - plus the gradient of the sources (added under ABI 7, nothing existing
+ * changed): gx NHWC [B][h][w][gx_stride >= c_x] takes the columns of x, gx2 NHWC [B][h][w][gx2_stride >= c_x2] those of x2; either
+ * may be NULL (its columns are skipped), both NULL is CF_ERR_ARG, as are a stride below the channel count and gx2 without x2.
+ *   dX[b][y][x][c] = sum over taps (dy,dx) and o < 256 of G0[b][y-dy][x-dx][o] * W0[o][c][1+dy][1+dx]
+ * with G0 the masked gradient of the first layer's pre-activation.  The call zeroes gx / gx2 whole (padding channels included),
+ * once; one launch per chunk of the list then scatters 32 positions x 32 channels per wave to the nine neighbours of each pixel
+ * with float atomics (neighbours outside the image receive nothing): like gw / gb, the last bits can differ from run to run; an
+ * all-zero gy gives exact zeros.  The workspace holds a second packed copy of W0 behind cf_head_backward's regions. */
+int cf_head_backward_dx(const cf_head_train_args* a, float* gx, int gx_stride, float* gx2, int gx2_stride, void* stream);
+size_t cf_head_bwd_dx_workspace_bytes(int B, int h, int w, int Cin, int n_hidden, int chunk_px);
 
 /* Training targets: the collated batch of the reference's dataset for B images, built on the device from packed annotation
  * tables (csrc/cf_targets.hip; added under ABI 7, nothing existing changed).  replaces: the loop over annotations of
