@@ -171,6 +171,7 @@ SYMBOLS = {
     "cf_stem_fused_early": (_i, [C.POINTER(StemEarlyArgs), _f]),
     "cf_split_bf16": (_i, [_f, _f, C.c_long, _i, _i, _i, _f]),
     "cf_head_fused": (_i, [C.POINTER(HeadFusedArgs), _f]),
+    "cf_head_fused_with": (_i, [C.POINTER(HeadFusedArgs), _i, _i, _f]),
     "cf_head_fused_at": (_i, [C.POINTER(HeadFusedArgs), _f, _i, _f]),
     "cf_head_slot_tables": (_i, [_f, _f, _i, _i, _i, _f, _f, _f]),
     "cf_pack_feat_mx": (_i, [_f, _i, _f, C.c_long, _f]),

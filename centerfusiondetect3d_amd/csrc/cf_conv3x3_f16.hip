@@ -26,27 +26,11 @@
 //
 // Replaces the 3x3 convolutions of model/networks/dla.py:42-62, 124-145 (BasicBlock conv1/conv2) and
 // the conv_offset_mask of model/networks/dla.py:406-414 (DeformConv) on the device.
-#include <stdlib.h>
 #include "cf_f16x3.h"
 
 namespace {
 
-#ifdef CF_CONV3_SHAPE16T
-// (dev timing arm, results are garbage: every v_mfma_f32_32x32x16_f16 becomes two v_mfma_f32_16x16x32_f16 on quarters of
-//  the same accumulator - the same FLOPs, LDS reads, weight loads and registers, only the MFMA shape differs.  Costs the
-//  16x16x32 rewrite of this kernel before building it: DESIGN.md section 9.)
-__device__ __forceinline__ f32x16 mfma_shape16(f16x8 a, f16x8 b, f32x16 c) {
-  f32x4 q0 = {c[0], c[1], c[2], c[3]}, q1 = {c[8], c[9], c[10], c[11]};
-  q0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, q0, 0, 0, 0);
-  q1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, q1, 0, 0, 0);
-  c[0] = q0[0]; c[1] = q0[1]; c[2] = q0[2]; c[3] = q0[3];
-  c[8] = q1[0]; c[9] = q1[1]; c[10] = q1[2]; c[11] = q1[3];
-  return c;
-}
-#define CF_MFMA_F16(a, b, c) mfma_shape16(a, b, c)
-#else
 #define CF_MFMA_F16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
-#endif
 
 struct Conv3F {
   const float* x;               // fp32 NHWC, first channel of the source
@@ -93,9 +77,9 @@ struct Conv3G {
 // plus a one-pixel frame, (R/16 + 2) x 18 rows, zero-filled outside the image - so no tap needs a
 // validity select and the tap offsets are compile-time constants.  Pays on wide maps (W = 200: 1.3x
 // input traffic instead of 2.6x) whenever W is close to a multiple of 16.
-// CT = 32-pixel column tiles per wave: 2 (64 x 64 wave tiles, two waves per SIMD at 256 registers each) or 4 - the
-// ONE-WAVE-PER-SIMD form (MINB = 1, 512 registers: both accumulator sets of a 64-channel x 128-pixel tile, 256 registers,
-// sit in AGPRs; every weight fragment is fetched once per 128 pixels instead of once per 64).
+// CT = 32-pixel column tiles per wave: 2 (64 x 64 wave tiles, two waves per SIMD at 256 registers each) or 1 (half-size
+// tiles for small grids, below).  The kernel is generic in CT; the one-wave-per-SIMD form CT = 4 (MINB = 1, 512 registers:
+// both accumulator sets of a 64-channel x 128-pixel tile in AGPRs) measured slower and is not instantiated: DESIGN.md section 9.
 // ROOT (BasicBlock conv2 of a one-level Tree without children, dla.py:105-118, 33-41; N = 64 WC channels, all of them in
 // this workgroup): the Tree's Root - ReLU(W_root . [x2; x1] + b), x2 = this convolution's output, x1 = its residual -
 // runs from the epilogue.  Every wave splits its 64 channels of x2 (bias, residual, ReLU applied) and of x1 to fp16
@@ -301,73 +285,17 @@ static int conv3x3_impl(const cf_conv_args* a, const cf_conv_args* root, const i
   if (s2) {
     // stride 2: 4 x 16 or 8 x 16 output tiles by output width; a geometry the patch does not fit goes to the slot kernel
     k.n_rounds = slices;
-    static const int alt = [] { const char* e = getenv("CF_CONV3_S2_ALT"); return e ? atoi(e) : 0; }();   // (dev A/B: other tile heights)
     if (a->N_pad == 64) ok = try_launch<1, 4, 1, 2, 9, false, 2, true, 1, true>(k, a->B, st);
-    else if (a->N_pad == 128) ok = (alt & 1) ? try_launch<2, 2, 1, 2, 9, false, 2, true, 2, true>(k, a->B, st)
-                                             : try_launch<2, 2, 1, 2, 5, true, 2, true, 1, true>(k, a->B, st);
+    else if (a->N_pad == 128) ok = try_launch<2, 2, 1, 2, 5, true, 2, true, 1, true>(k, a->B, st);
     else if (a->N_pad >= 256) {
       // half-height tiles (2 x 16) while that grid still fits the chip in one round (level 5 of a bs <= 8 launch: 34.5 vs
       // 47.9 us); same sums whatever the tile, so this may depend on the batch size (as the stride-1 small-grid rule)
       const long half_tiles = (long)((a->Ho + 1) / 2) * ((a->Wo + 15) / 16) * a->B * ((a->N_pad + 255) / 256);
-      ok = ((alt & 2) || half_tiles <= 256) ? try_launch<4, 1, 1, 2, 3, true, 2, true, 1, true>(k, a->B, st)
-           : (alt & 4)                      ? try_launch<4, 2, 1, 2, 5, true, 1, true, 1, true>(k, a->B, st)
-                                            : try_launch<4, 1, 1, 2, 5, true, 2, true, 2, true>(k, a->B, st);
+      ok = half_tiles <= 256 ? try_launch<4, 1, 1, 2, 3, true, 2, true, 1, true>(k, a->B, st)
+                             : try_launch<4, 1, 1, 2, 5, true, 2, true, 2, true>(k, a->B, st);
     }
     if (!ok) return cf_conv2d_f16x3(a, stream);
     return cf_check_launch("cf_conv3x3_f16x3");
-  }
-  // dev override (tools/bench_conv_cfg.py): CF_CONV3_CFG="WC,WP,WK[,T2]" forces one of the instantiated tilings
-  static const int only_n = [] { const char* e = getenv("CF_CONV3_ONLY_N"); return e ? atoi(e) : 0; }();   // (dev: override one width only)
-  if (const char* force = (!proj_ch && (only_n == 0 || only_n == a->N_pad)) ? getenv("CF_CONV3_CFG") : nullptr) {
-    int wc = 0, wp = 0, wk = 0, t2f = 0, ct = 2, rt = 2;
-    if (sscanf(force, "%d,%d,%d,%d,%d,%d", &wc, &wp, &wk, &t2f, &ct, &rt) >= 3 && cfg(wk)) {
-      const int key = wc * 100 + wp * 10 + wk;
-      bool done = false;
-      if (a->N_pad >= 64 && ct == 1) {              // half-size pixel tiles (32 pixels per wave): small grids, see below
-        switch (key) {
-          case 221: done = try_launch<2, 2, 1, 2, 4, true, 2, false, 1>(k, B, st); break;
-          case 411: done = try_launch<4, 1, 1, 2, 4, true, 2, false, 1>(k, B, st); break;
-          case 212: done = try_launch<2, 1, 2, 2, 4, true, 2, false, 1>(k, B, st); break;
-          case 141: done = t2f ? try_launch<1, 4, 1, 2, 4, true, 2, true, 1>(k, B, st) : try_launch<1, 4, 1, 2, 6, true, 2, false, 1>(k, B, st); break;
-          default: break;
-        }
-      } else
-#ifdef CF_ONESET
-      if (a->N_pad >= 64 && ct == 4 && rt == 2) {   // 64-channel x 128-pixel wave tiles at TWO waves per SIMD (one accumulator set)
-        switch (key) {
-          case 141: done = t2f && try_launch<1, 4, 1, 2, 10, true, 2, true, 4>(k, B, st); break;
-          case 221: done = t2f ? try_launch<2, 2, 1, 2, 6, true, 2, true, 4>(k, B, st) : try_launch<2, 2, 1, 2, 8, true, 2, false, 4>(k, B, st); break;
-          case 411: done = t2f ? try_launch<4, 1, 1, 2, 4, true, 2, true, 4>(k, B, st) : try_launch<4, 1, 1, 2, 4, true, 2, false, 4>(k, B, st); break;
-          default: break;
-        }
-      } else
-#endif
-      if (a->N_pad >= 64 && ct == 4 && rt == 1) {   // 32-channel x 128-pixel wave tiles, two waves per SIMD: half the weight stream
-        switch (key) {
-          case 221: done = t2f && try_launch<2, 2, 1, 1, 6, true, 2, true, 4>(k, B, st); break;   // (the flat forms of these two spill)
-          case 411: done = t2f && try_launch<4, 1, 1, 1, 4, true, 2, true, 4>(k, B, st); break;
-          case 421: done = t2f ? try_launch<4, 2, 1, 1, 4, true, 1, true, 4>(k, B, st) : try_launch<4, 2, 1, 1, 4, true, 1, false, 4>(k, B, st); break;
-          default: break;
-        }
-      } else if (a->N_pad >= 64 && ct == 4) {       // one wave per SIMD, 64 x 128 wave tiles
-        switch (key) {
-          case 141: done = t2f ? try_launch<1, 4, 1, 2, 10, true, 1, true, 4>(k, B, st) : try_launch<1, 4, 1, 2, 16, true, 1, false, 4>(k, B, st); break;
-          case 221: done = try_launch<2, 2, 1, 2, 8, true, 1, false, 4>(k, B, st); break;
-          case 411: done = try_launch<4, 1, 1, 2, 4, true, 1, false, 4>(k, B, st); break;
-          default: break;
-        }
-      } else if (a->N_pad >= 64) {
-        switch (key) {
-          case 221: done = try_launch<2, 2, 1, 2, 6, true, 2>(k, B, st); break;
-          case 212: done = try_launch<2, 1, 2, 2, 4, true, 2>(k, B, st); break;
-          case 411: done = try_launch<4, 1, 1, 2, 4, true, 2>(k, B, st); break;
-          case 421: done = try_launch<4, 2, 1, 2, 2, true, 1>(k, B, st); break;
-          case 141: done = t2f ? try_launch<1, 4, 1, 2, 6, true, 2, true>(k, B, st) : try_launch<1, 4, 1, 2, 6, true, 2>(k, B, st); break;
-          default: break;
-        }
-      }
-      if (done) return cf_check_launch("cf_conv3x3_f16x3");
-    }
   }
   const bool big = (long)a->H * a->W >= 4096;     // (never a function of the batch size: WK changes the
                                                   //  summation order, and a shard of a batch has to
@@ -380,8 +308,7 @@ static int conv3x3_impl(const cf_conv_args* a, const cf_conv_args* root, const i
   // gone).  The tile shape changes no sum (same K order, same WK): results are bit-identical, so this MAY depend on the
   // batch size; the patch is tiled (8 x 16) whatever the map - tile quantisation costs nothing on an empty chip.
   const long tiles8x16 = (long)((a->H + 7) / 8) * ((a->W + 15) / 16) * B;
-  static const long round_wgs = [] { const char* e = getenv("CF_CONV3_ONE_ROUND"); return e ? atol(e) : 256L; }();   // (dev A/B of the threshold)
-  auto one_round = [&](long wgs) { return wgs <= round_wgs; };
+  auto one_round = [](long wgs) { return wgs <= 256; };
   if (a->N_pad == 32) {
     if (big && cfg(1) && one_round(tiles8x16)) ok = try_launch<1, 4, 1, 1, 4, true, 2, true, 1>(k, B, st);
     if (ok) {
@@ -397,8 +324,8 @@ static int conv3x3_impl(const cf_conv_args* a, const cf_conv_args* root, const i
     if (cfg(1)) ok = (one_round(tiles8x16) && launch_p<1, 4, 1, 2, 4, true, 2, true, 1>(k, B, st)) ||
                      (t2 && launch_p<1, 4, 1, 2, 6, true, 2, true>(k, B, st)) || launch_p<1, 4, 1, 2, 6, true, 2>(k, B, st);
   } else if (a->N_pad == 128) {
-    // (the one-wave-per-SIMD form - CT = 4, 64-channel x 128-pixel wave tiles, accumulators in AGPRs, CF_CONV3_CFG
-    //  "2,2,1,0,4" - is bit-identical and measured 97-123 us against 76-92 us here: DESIGN.md section 9)
+    // (the one-wave-per-SIMD form - CT = 4, 64-channel x 128-pixel wave tiles, accumulators in AGPRs - was bit-identical
+    //  and measured 97-123 us against 76-92 us here: DESIGN.md section 9)
     // wide maps (3x896x1600: level 3 is 112 x 200): 8 x 16 tiles with a frame - the flat run's patch (R + 2W + 2 rows)
     // no longer fits, and falling back to the slot kernel re-gathers every input 9 times
     if (cfg(1)) ok = (one_round(2 * tiles8x16) && launch_p<1, 4, 1, 2, 4, true, 2, true, 1>(k, B, st)) ||   // (64 channels per workgroup)
@@ -469,9 +396,7 @@ extern "C" int cf_conv3x3_root_f16x3(const cf_conv_args* a, const cf_conv_args* 
   bool fused = false;
   const bool fusable = (a->N == 64 || a->N == 128 || a->N == 256) && a->N_pad == a->N && r->N == a->N &&
                        r->N_pad == a->N && pieces_ok && r->K_pad == k_sum && a->res_stride % 4 == 0 && r->out_stride % 4 == 0;
-  static const int fuse_on = [] { const char* e = getenv("CF_ROOT_FUSE"); return e ? atoi(e) : 1; }();   // (dev A/B: 0 off, 1 on, 2 on without children)
-  const bool want = fusable && fuse_on && (fuse_on == 1 || r->n_src == 2);
-  const int rc = conv3x3_impl(a, want ? r : nullptr, root_channels, &fused, stream);
+  const int rc = conv3x3_impl(a, fusable ? r : nullptr, root_channels, &fused, stream);
   if (rc != CF_OK || fused) return rc;
   return cf_conv2d_f16x3(r, stream);
 }

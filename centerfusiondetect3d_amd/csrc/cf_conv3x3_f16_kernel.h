@@ -26,13 +26,6 @@ __global__ __launch_bounds__(64 * WC * WP * WK, MINB) void conv3x3_f16x3_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, h = lane >> 5;
   const int wk = wave % WK, wp = (wave / WK) % WP, wc = wave / (WK * WP);
-#ifdef CF_CONV3_PROF   // dev (tools/prof_conv3.py): cycles per phase of thread 0, written over its first output values
-  long long t_prof[4] = {0, 0, 0, 0};
-  long long t_last = clock64();
-#define PROF_MARK(i) { const long long t_now = clock64(); t_prof[i] += t_now - t_last; t_last = t_now; }
-#else
-#define PROF_MARK(i)
-#endif
   // consecutive tiles on ONE XCD (cf_xcd_remap): neighbouring patches overlap, and every round
   // re-touches the same rows - both should hit that XCD's L2
 #if CF_CONV3_GROUPED
@@ -98,9 +91,6 @@ __global__ __launch_bounds__(64 * WC * WP * WK, MINB) void conv3x3_f16x3_kernel(
   f32x4 raw[NU];
   auto load_patch = [&](int r, int lo, int hi) {
     const int c0 = r * 16 * WK;
-#ifdef CF_CONV3_NOPATCH   // (dev timing experiment: the patch is fetched once per tile, later rounds re-split the same rows)
-    if (r > 0) return;
-#endif
 #pragma unroll
     for (int it = 0; it < NU; ++it) {
       if (it < lo || it >= hi) continue;
@@ -108,9 +98,6 @@ __global__ __launch_bounds__(64 * WC * WP * WK, MINB) void conv3x3_f16x3_kernel(
     }
   };
   auto store_patch = [&](unsigned char* buf, int lo, int hi) {
-#ifdef CF_CONV3_NOSTAGE   // (dev timing experiment: no operand split / LDS store behind the first patch)
-    if (buf != smem) return;
-#endif
     int tid_s = threadIdx.x;                 // (laundered: the NU destination addresses are re-derived per call - 3 ALU
     asm volatile("" : "+v"(tid_s));          //  instructions each - instead of living in registers / scratch all loop long)
 #pragma unroll
@@ -171,9 +158,6 @@ __global__ __launch_bounds__(64 * WC * WP * WK, MINB) void conv3x3_f16x3_kernel(
   // 32-bit offset register serves every weight load of the kernel
   const unsigned lane16 = (unsigned)lane * 16u;
   auto load_w = [&](f16x8 (&dh)[RT], f16x8 (&dl)[RT], int ks) {
-#ifdef CF_CONV3_NOWEIGHT  // (dev timing experiment: weight fragments fetched for the first three taps only)
-    if (ks > wk * 9 + 2) return;
-#endif
     ks = min(ks, ks_last);
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
@@ -188,7 +172,6 @@ __global__ __launch_bounds__(64 * WC * WP * WK, MINB) void conv3x3_f16x3_kernel(
   for (int t = 0; t < 3; ++t) load_w(wh[t], wl[t], wk * 9 + t);
   store_patch(smem, 0, NU);
   __syncthreads();
-  PROF_MARK(0)
 
   for (int r = 0; r < p.n_rounds; ++r) {
     const unsigned char* cur = smem + (DB ? (r & 1) * bufb : 0);
@@ -222,11 +205,7 @@ __global__ __launch_bounds__(64 * WC * WP * WK, MINB) void conv3x3_f16x3_kernel(
       for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
-#ifdef CF_ONESET   // (dev timing experiment: all three products into ONE accumulator set - fails the float64 RMS gate)
-          accm[rt][ct] = CF_MFMA_F16(wl[t % 3][rt], xh[t & 1][ct], accm[rt][ct]);
-#else
           accs[rt][ct] = CF_MFMA_F16(wl[t % 3][rt], xh[t & 1][ct], accs[rt][ct]);
-#endif
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -236,11 +215,7 @@ __global__ __launch_bounds__(64 * WC * WP * WK, MINB) void conv3x3_f16x3_kernel(
       for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
-#ifdef CF_ONESET
-          accm[rt][ct] = CF_MFMA_F16(wh[t % 3][rt], xl[ct], accm[rt][ct]);
-#else
           accs[rt][ct] = CF_MFMA_F16(wh[t % 3][rt], xl[ct], accs[rt][ct]);
-#endif
       // tap t+3 of this round, or tap t-6 of the next one (same set either way)
       load_w(wh[t % 3], wl[t % 3], t + 3 < 9 ? ks0 + t + 3 : ks0 + 9 * WK + t - 6);
       if (DB && t == 3 && more) {            // first half of the next patch: split + store, then request the rest
@@ -249,7 +224,6 @@ __global__ __launch_bounds__(64 * WC * WP * WK, MINB) void conv3x3_f16x3_kernel(
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    PROF_MARK(1)
     if (!DB) {
       __syncthreads();                       // single buffer: everyone is done reading it
       if (more) {
@@ -258,10 +232,7 @@ __global__ __launch_bounds__(64 * WC * WP * WK, MINB) void conv3x3_f16x3_kernel(
       }
     }
     if (more) store_patch(nxt, NH0, NU);
-#ifndef CF_CONV3_NOBARRIER   // (dev timing experiment: results are garbage without it)
     __syncthreads();
-#endif
-    PROF_MARK(2)
   }
 
   // ---- PROJ: the projection's k-steps, behind the 3x3 part (the patch is dead: its memory holds the B tiles)
@@ -692,14 +663,5 @@ __global__ __launch_bounds__(64 * WC * WP * WK, MINB) void conv3x3_f16x3_kernel(
         }
       }
   }
-#ifdef CF_CONV3_PROF
-  PROF_MARK(3)
-  if (tid == 0 && blockIdx.y == 0) {
-    const int pl = 0;
-    size_t m = m0 + pl;
-    if (T2) m = m0 + (size_t)ty0 * p.W + tx0;
-    for (int i = 0; i < 4; ++i) p.out[m * p.out_stride + i] = (float)t_prof[i];
-  }
-#endif
 }
 

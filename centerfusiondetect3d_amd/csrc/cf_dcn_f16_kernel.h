@@ -48,26 +48,11 @@ __global__ __launch_bounds__(256, 2) void dcn_f16x3_kernel(DcnF p) {
   const bool w_ok = rt0 < p.n_rt;
   const int n_ks = p.n_chunks * 2;
   const int HW = p.H * p.W;
-#ifdef CF_DCN_PROF   // dev (tools/prof_dcn.py): cycles per phase of thread 0, written over its first output values
-  long long t_prof[4] = {0, 0, 0, 0};
-  long long t_last = clock64();
-#define DPROF_MARK(i) { const long long t_now = clock64(); t_prof[i] += t_now - t_last; t_last = t_now; }
-#else
-#define DPROF_MARK(i)
-#endif
 
   // (all offset / mask values of the tile are requested before the first is used: one memory round trip for the phase
   //  instead of one per descriptor - it was 13 % of a 64-channel layer's workgroup time)
   constexpr int NDI = (PXB * 9 + 255) / 256;
   float omy[NDI], omx[NDI], omm[NDI];
-#ifdef CF_DCN_NODESC        // (dev timing experiment: no descriptor phase - every sample is the pixel's own cell with weight 1, 0, 0, 0)
-  for (int i = tid; i < PXB * 9; i += 256) {
-    const int m = min(m0 + i / 9, p.M - 1);
-    desc[2 * i] = f32x4{__int_as_float(m * p.C), __int_as_float(0), __int_as_float(0), p.in_scale};
-    desc[2 * i + 1] = f32x4{1.0f, 0.0f, 0.0f, 0.0f};
-  }
-  if (false)
-#endif
 #pragma unroll
   for (int it = 0; it < NDI; ++it) {
     const int i = min(tid + 256 * it, PXB * 9 - 1);
@@ -77,9 +62,6 @@ __global__ __launch_bounds__(256, 2) void dcn_f16x3_kernel(DcnF p) {
     omx[it] = om[2 * tap + 1];
     omm[it] = om[18 + tap];
   }
-#ifdef CF_DCN_NODESC
-  if (false)
-#endif
 #pragma unroll
   for (int it = 0; it < NDI; ++it) {
     const int i = tid + 256 * it;
@@ -116,19 +98,14 @@ __global__ __launch_bounds__(256, 2) void dcn_f16x3_kernel(DcnF p) {
     desc[2 * i + 1] = dB;
   }
   __syncthreads();
-  DPROF_MARK(0)
 
   // corner samples are requested TWO chunks ahead (sets c & 1): the texture path, which bounds the
   // 64-channel layers, then always has a full chunk of requests queued behind the one being blended
   // (DEEP only for the two-pixel-group configuration: with WP = 1 the second set costs an occupancy
   //  step or spills and measured slower)
   // (... and for the half-size tiles, CT = 1: one set keeps them at 114 registers = FOUR workgroups per CU, which beats the
-  //  deeper queue at three: 8 x 64 -> 64 at 112 x 200 106-108 vs 115-116 us, step 7.53 vs 7.63 ms.  CF_DCN_DEEP1: dev A/B)
-#ifdef CF_DCN_DEEP1
-  constexpr bool DEEP = WP == 2;
-#else
+  //  deeper queue at three: 8 x 64 -> 64 at 112 x 200 106-108 vs 115-116 us, step 7.53 vs 7.63 ms)
   constexpr bool DEEP = WP == 2 && CT == 2;
-#endif
   constexpr int NSET = DEEP ? 2 : 1;
   f32x4 cvs[NSET][NP][4][2];   // 4 corners x 8 channels
   f32x4 cws[NSET][NP];         // corner weights
@@ -141,17 +118,10 @@ __global__ __launch_bounds__(256, 2) void dcn_f16x3_kernel(DcnF p) {
       const f32x4 dA = desc[e];
       cw[i] = desc[e + 1];
       cmk[i] = dA[3];
-#ifdef CF_DCN_NOGATHER    // (dev timing experiment: every corner from one line - what the kernel costs without the gather)
-      const float* a0 = p.x + ((__float_as_int(dA[0]) & 0) + c0);
-#else
       const float* a0 = p.x + (__float_as_int(dA[0]) + c0);
-#endif
       const float* a1 = a0 + __float_as_int(dA[1]);
       const float* a2 = a0 + __float_as_int(dA[2]);
       const float* a3 = a2 + __float_as_int(dA[1]);
-#ifdef CF_DCN_NOLOAD      // (dev timing experiment: no corner requests at all behind the first chunk of a tile)
-      if (c > 1) return;
-#endif
       cv[i][0][0] = *reinterpret_cast<const f32x4*>(a0);
       cv[i][0][1] = *reinterpret_cast<const f32x4*>(a0 + 4);
       cv[i][1][0] = *reinterpret_cast<const f32x4*>(a1);
@@ -171,14 +141,6 @@ __global__ __launch_bounds__(256, 2) void dcn_f16x3_kernel(DcnF p) {
     for (int i = 0; i < NP; ++i) {
       const int pr = tid + 256 * i;
       const float mk = cmk[i];   // the mask (x 2^4 activation scale) is applied after the 4-corner sum, as the reference does
-#ifdef CF_DCN_NOBLEND       // (dev timing experiment: no blend / split arithmetic, the first corner's bits are staged as they are)
-      {
-        unsigned char* o = buf + (pr >> 2) * FROWB + (pr & 3) * 16;
-        *reinterpret_cast<f32x4*>(o) = cv[i][0][0] * mk;
-        *reinterpret_cast<f32x4*>(o + PLANE) = cv[i][0][1];
-        continue;
-      }
-#endif
       // explicit vector FMAs (v_pk_fma_f32: two channels per instruction)
       f32x4 v0 = cw[i][0] * cv[i][0][0], v1 = cw[i][0] * cv[i][0][1];
 #pragma unroll
@@ -226,15 +188,6 @@ __global__ __launch_bounds__(256, 2) void dcn_f16x3_kernel(DcnF p) {
       xh[ct] = *reinterpret_cast<const f16x8*>(row);
       xl[ct] = *reinterpret_cast<const f16x8*>(row + PLANE);
     }
-#ifdef CF_DCN_NOMFMA       // (dev timing experiment: ONE MFMA per k-step that still consumes every operand register)
-    {
-      f16x8 a = al[0] + ah[0], b = xh[0] + xl[0] + xh[CT - 1] + xl[CT - 1];
-#pragma unroll
-      for (int rt = 1; rt < RT; ++rt) a += al[rt] + ah[rt];
-      accm[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, accm[0][0], 0, 0, 0);
-      return;
-    }
-#endif
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -273,8 +226,7 @@ __global__ __launch_bounds__(256, 2) void dcn_f16x3_kernel(DcnF p) {
     // load is unconditional (no exec-masked operand load inside a pinned loop).  Bit-identical to
     // the plain form.  Measured (tools/bench_dcn.py, same box): 256 -> 128 at 28 x 50: 86.4 vs 93.0 us; the two-group tiles
     // of the 64-channel layers LOSE with it (254 vs 212 us, 149 vs 131 us: every wait for a corner or an LDS fragment then
-    // also holds back the wave's next MFMA), so they keep the compiler's order.  CF_DCN_NOPIN: dev A/B.
-#ifndef CF_DCN_NOPIN
+    // also holds back the wave's next MFMA), so they keep the compiler's order.
     if constexpr (WP == 1 && CT == 2)
     {
       f32x4 bv[2];                           // blended 8 channels of the pair in progress
@@ -338,22 +290,15 @@ __global__ __launch_bounds__(256, 2) void dcn_f16x3_kernel(DcnF p) {
       __syncthreads();
       return;
     }
-#endif
     mma_kstep(cur, 0, wh[0], wl[0]);
-#ifndef CF_DCN_NOWEIGHT   // (dev timing experiment: the weight stream's share of the texture path - DESIGN.md section 9)
     if (j + 1 < n_own) load_w(wh[0], wl[0], 2 * c + 2);
-#endif
     mma_kstep(cur, 1, wh[1], wl[1]);
     if (j + 1 < n_own) {
-#ifndef CF_DCN_NOWEIGHT
       load_w(wh[1], wl[1], 2 * c + 3);
-#endif
       store_b(nxt, cv, cw, cmk);
       if (j + 1 + NSET < n_own) load_b(c + 1 + NSET, cv, cw, cmk);
     }
-#ifndef CF_DCN_NOBARRIER   // (dev timing experiment: what the per-chunk workgroup barrier costs; results are garbage)
     __syncthreads();
-#endif
   };
   if (DEEP) {
     for (int j = 0; j < n_own; j += 2) {
@@ -364,7 +309,6 @@ __global__ __launch_bounds__(256, 2) void dcn_f16x3_kernel(DcnF p) {
     for (int j = 0; j < n_own; ++j) iteration(j, cvs[0], cws[0], cmks[0]);
   }
 
-  DPROF_MARK(1)
   if (gridDim.z > 1) {   // raw partial sums; scale / bias / activation happen in the reduction
     const int ns = p.n_rt * 32;
 #pragma unroll
@@ -393,19 +337,6 @@ __global__ __launch_bounds__(256, 2) void dcn_f16x3_kernel(DcnF p) {
   // LDS tile (free after the loop's last barrier) and writes whole pixel rows - RT*128 contiguous bytes per pixel
   // instead of 32-byte pieces - and the split-bf16 copy as 8-byte pieces that are contiguous across lanes.
   constexpr bool coalesced = COAL;        // (the host selects it: N % 4 == 0)
-#ifdef CF_DCN_NOEPI         // (dev timing experiment: no output transposition / stores - one conditional store keeps the sums alive)
-  {
-    float sum = 0.0f;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sum += accm[rt][ct][r] + accs[rt][ct][r];
-    if (sum == 12345.0f) p.out[tid] = sum;
-    return;
-  }
-#endif
   if (coalesced && w_ok) {
     constexpr int EROW = RT * 128 + 16;
     constexpr int LPP = RT * 8, PPI = 64 / LPP;
@@ -518,10 +449,5 @@ __global__ __launch_bounds__(256, 2) void dcn_f16x3_kernel(DcnF p) {
         }
       }
   }
-#ifdef CF_DCN_PROF
-  DPROF_MARK(2)
-  if (tid == 0 && blockIdx.y == 0 && m0 < p.M)
-    for (int i = 0; i < 3; ++i) p.out[(size_t)m0 * p.out_stride + i] = (float)t_prof[i];
-#endif
 }
 

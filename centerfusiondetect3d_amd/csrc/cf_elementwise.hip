@@ -2,7 +2,6 @@
 // 2x2 max-pool, the layout changes at the module boundary and the fp32 -> split-bf16 conversion.
 // All are one-pass streaming kernels: 16 B per lane, channel-innermost (NHWC) so every
 // wave-instruction touches whole lines.
-#include <stdlib.h>
 #include "cf_common.h"
 
 namespace {
@@ -275,10 +274,9 @@ extern "C" int cf_upsample_dw(const float* x, const float* weight, const float* 
   const int row_len = W * f * (C / 4);
   const dim3 grid((unsigned)((row_len + 255) / 256), (unsigned)(H * f), (unsigned)B);
   hipStream_t st = (hipStream_t)stream;
-  // f = 2 with a channel-group count that divides the workgroup: 2 x 2 output blocks per thread (same sums, same order).
-  // CF_UPSAMPLE_BLOCK=0: dev A/B against the per-pixel kernel.
-  static const int block_on = [] { const char* e = getenv("CF_UPSAMPLE_BLOCK"); return e ? atoi(e) : 1; }();
-  if (f == 2 && block_on && 256 % (C / 4) == 0) {
+  // f = 2 with a channel-group count that divides the workgroup: 2 x 2 output blocks per thread (same sums, same order);
+  // other channel counts take the per-pixel kernel below.
+  if (f == 2 && 256 % (C / 4) == 0) {
     const dim3 g2((unsigned)((W * (C / 4) + 255) / 256), (unsigned)H, (unsigned)B);
     hipLaunchKernelGGL(upsample2_block_kernel, g2, dim3(256), 0, st, x, weight, skip, out, H, W, C / 4);
     return cf_check_launch("cf_upsample_dw");

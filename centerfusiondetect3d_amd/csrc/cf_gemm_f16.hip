@@ -21,7 +21,6 @@
 // per 32-deep chunk.  Workgroup = 4 waves as WC (channel groups) x WP (pixel groups); a wave owns
 // RT*32 output channels x 64 pixels.  Accumulators have pixels on lanes and 4 consecutive channels
 // per register group, so the fp32 NHWC store is one 16-byte write per lane and group.
-#include <stdlib.h>
 #include "cf_f16x3.h"
 #include "cf_mx.h"
 
@@ -255,7 +254,7 @@ struct DcnF {
   int split_stride;
   unsigned char* out_mx; // optional mx rows [M][272] (cf_pack_feat_mx's format; N = 64, one 32-channel row tile per wave)
   float* partial;        // K split (gridDim.z > 1): raw partial sums [z][M][n_rt * 32], reduced by dcn_reduce_kernel
-  int direct_epilogue;   // dev A/B (CF_DCN_EPI=0): store the accumulators directly
+  int direct_epilogue;   // always 0: no kernel reads it, it only keeps its slot in the argument block
   int mask_activated;    // offmask channels 18..26 are modulation factors already (no sigmoid here)
 };
 
@@ -460,19 +459,13 @@ static int dcn_f16x3_impl(const cf_dcn_args* a, const cf_dcn_args* const* gs, in
     hipLaunchKernelGGL(kernel_g, grid, dim3(256), 0, st, k, g);
   };
   k.mask_activated = a->mask_activated;
-  static const int direct_epi = [] { const char* e = getenv("CF_DCN_EPI"); return e ? atoi(e) == 0 : 0; }();
-  k.direct_epilogue = direct_epi;
-  const bool coal = (a->N & 3) == 0 && !k.direct_epilogue;   // whole-row epilogue through LDS
-  CF_REQUIRE(!a->out_mx || coal, "cf_dcn_v2_f16x3: the mx output is written by the whole-row epilogue (CF_DCN_EPI=0 disables it)");
+  const bool coal = (a->N & 3) == 0;   // whole-row epilogue through LDS
+  CF_REQUIRE(!a->out_mx || coal, "cf_dcn_v2_f16x3: the mx output is written by the whole-row epilogue (N %% 4 == 0)");
   // SMALL GRIDS (small batches): 64 output channels on 64-pixel tiles (the 128-channel configuration with two of its
   // four channel-group waves idle in the MFMAs, all four staging) while that launch still fits the chip in one round:
   // 128 -> 64 at 56x100, bs=1: 30.4 vs 43.4 us, bs=2: 31.6 vs 45.0 us; at 350 workgroups the gain is gone.  Same K order,
   // same K split: bit-identical, so the choice may depend on the batch size (as in cf_conv3x3_f16x3).
-#ifdef CF_DCN_SMALLTILE     // (dev timing experiment: the 64-pixel-tile configuration at every grid size)
-  if (a->N_pad <= 64) {
-#else
   if (a->N_pad <= 64 && (M + 63) / 64 * (long)ks * G <= 256) {
-#endif
     const dim3 grid((unsigned)((M + 63) / 64), 1u, ks);
     if (coal) launch(dcn_f16x3_kernel<4, 1, 1, true>, dcn_f16x3_kernel_grouped<4, 1, 1, true>, grid);
     else launch_f16(dcn_f16x3_kernel<4, 1, 1, false>, grid, 0, st, k);
@@ -480,12 +473,10 @@ static int dcn_f16x3_impl(const cf_dcn_args* a, const cf_dcn_args* const* gs, in
     // half-size pixel tiles (32 pixels per wave: 114 registers, 39 KB of LDS - four workgroups per CU instead of two): the parts
     // of this kernel add up instead of overlapping (docs/experiments/r5_dcn_attribution.md), so a third wave per SIMD pays
     // wherever the grid is not many rounds deep - 8 x 64 -> 64 at 112 x 200: 116.5 vs 123.5 us, 8 x 128 -> 64 at 56 x 100: 61.1 vs
-    // 72.6 us, 16 x 64 -> 64 at 112 x 200: equal; step 7.75 vs 7.80 ms.  Same K order: bit-identical.  CF_DCN_CT1=0: dev A/B.
-    static const int ct1 = [] { const char* e = getenv("CF_DCN_CT1"); return e ? atoi(e) : 1; }();
+    // 72.6 us, 16 x 64 -> 64 at 112 x 200: equal; step 7.75 vs 7.80 ms.  Same K order: bit-identical.
     const dim3 grid((unsigned)((M + 127) / 128), (unsigned)((a->N_pad + 63) / 64), ks);
     const dim3 grid1((unsigned)((M + 63) / 64), (unsigned)((a->N_pad + 63) / 64), ks);
-    if ((ct1 || gs) && coal) launch(dcn_f16x3_kernel<2, 2, 1, true, 1>, dcn_f16x3_kernel_grouped<2, 2, 1, true, 1>, grid1);
-    else if (coal) launch_f16(dcn_f16x3_kernel<2, 2, 1, true>, grid, 0, st, k);
+    if (coal) launch(dcn_f16x3_kernel<2, 2, 1, true, 1>, dcn_f16x3_kernel_grouped<2, 2, 1, true, 1>, grid1);
     else launch_f16(dcn_f16x3_kernel<2, 2, 1, false>, grid, 0, st, k);
   } else if (a->N_pad <= 128) {  // 128 channels: 4 x 32-channel wave rows, 64 pixels
     const dim3 grid((unsigned)((M + 63) / 64), (unsigned)((a->N_pad + 127) / 128), ks);
@@ -533,8 +524,6 @@ extern "C" int cf_dcn_v2_f16x3_grouped(const cf_dcn_args* const* gs, int32_t n_g
     CF_REQUIRE(b->offmask == a->offmask + g * M * a->om_stride && b->out == a->out + g * M * a->out_stride,
                "cf_dcn_v2_f16x3_grouped: group %d must use rows [g M, (g + 1) M) of group 0's offmask / out buffers", g);
   }
-  static const int direct_epi = [] { const char* e = getenv("CF_DCN_EPI"); return e ? atoi(e) == 0 : 0; }();
-  CF_REQUIRE(!direct_epi, "cf_dcn_v2_f16x3_grouped: CF_DCN_EPI=0 (dev) has no grouped form");
   return dcn_f16x3_impl(a, gs, n_groups, stream);
 }
 

@@ -20,7 +20,6 @@
 // In the hidden layers wave w of the 4 owns output channels [64w, 64w+64) x the 64 pixels of a half tile (4x4 16x16
 // accumulators) whose [64 px][256 ch] hi and lo planes (66 KiB) stay in LDS for the whole chain; in the output layer
 // the 4 waves split K instead and their partial sums are reduced through LDS.
-#include <stdlib.h>
 #include <string>
 #include "cf_common.h"
 #include "cf_mx.h"
@@ -553,27 +552,10 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       sa = (int)__builtin_amdgcn_raw_buffer_load_b32(rs, l4, 14336, 0);
     };
     // one half (tile rows 4 hf .. 4 hf + 3) of a main k-step / one pair (tile rows 2 pr, 2 pr + 1) of a cross step
-#ifdef CF_MX_ARM_NOB       // dev timing arm (garbage results): the B fragments are read once, before the loop
-    hf16x8 xb_fix[4];
-    i32x8 xc_fix[2];
-    int sc_fix[2];
-    for (int ct = 0; ct < 4; ++ct) xb_fix[ct] = *reinterpret_cast<const hf16x8*>(xt + rowb[ct] + g * 64);
-    for (int c2 = 0; c2 < 2; ++c2) {
-      const unsigned char* r = xt + rowb[c2];
-      const u32x4 b0 = *reinterpret_cast<const u32x4*>(r + 64 * g + 32);
-      const u32x2 b1 = *reinterpret_cast<const u32x2*>(r + 64 * g + 48);
-      xc_fix[c2] = i32x8{(int)b0[0], (int)b0[1], (int)b0[2], (int)b0[3], (int)b1[0], (int)b1[1], 0, 0};
-      sc_fix[c2] = (int)(*reinterpret_cast<const unsigned*>(r + 256) >> (8 * g));
-    }
-#endif
     auto main_half = [&](const hf16x8 (&A)[4], int off, int hf) {
       hf16x8 xb[4];
 #pragma unroll
-#ifdef CF_MX_ARM_NOB
-      for (int ct = 0; ct < 4; ++ct) xb[ct] = xb_fix[(ct + hf + off / 16) & 3];      // (rotating: the operands still change from MFMA to MFMA)
-#else
       for (int ct = 0; ct < 4; ++ct) xb[ct] = *reinterpret_cast<const hf16x8*>(xt + rowb[4 * hf + ct] + off);
-#endif
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
@@ -590,10 +572,6 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
         const u32x2 b1 = *reinterpret_cast<const u32x2*>(r + 64 * g + 48);
         xb[c2] = i32x8{(int)b0[0], (int)b0[1], (int)b0[2], (int)b0[3], (int)b1[0], (int)b1[1], 0, 0};
         sb[c2] = (int)(*reinterpret_cast<const unsigned*>(r + 256) >> (8 * g));     // this lane's block: byte g -> byte 0
-#ifdef CF_MX_ARM_NOB
-        xb[c2] = xc_fix[(c2 + pr) & 1];
-        sb[c2] = sc_fix[(c2 + pr) & 1];
-#endif
       }
 #define CF_MX_ROW(RT)                                                                                                   \
       {                                                                                                                 \
@@ -618,23 +596,18 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
     for (int tap = 0; tap < 9; ++tap) {
       const int toff = ((tap / 3) * P_W + tap % 3) * ROWB;
       const int o0 = toff + g * 64, o1 = toff + g * 64 + 16;   // channels 0-31 / 32-63: lane group g holds 8 g .. 8 g + 7 of them
-#ifdef CF_MX_ARM_NOA       // dev timing arm (garbage results): no weight stream inside the loop
-#define CF_MX_LD(x)
-#else
-#define CF_MX_LD(x) x
-#endif
       main_half(am[0], o0, 0);
-      if (tap > 0) CF_MX_LD(ldx(tap));                     // (cross operands of THIS tap: freed by the item before)
+      if (tap > 0) ldx(tap);                               // (cross operands of THIS tap: freed by the item before)
       __builtin_amdgcn_sched_barrier(0);
       main_half(am[0], o0, 1);
       main_half(am[1], o1, 0);
-      if (tap + 1 < 9) CF_MX_LD(ldm(am[0], tap + 1, 0));
+      if (tap + 1 < 9) ldm(am[0], tap + 1, 0);
       else if (PC && HID == 1) ldp(ph, 0);
       __builtin_amdgcn_sched_barrier(0);
       main_half(am[1], o1, 1);
       cross_pair(toff, 0);
       cross_pair(toff, 1);
-      if (tap + 1 < 9) CF_MX_LD(ldm(am[1], tap + 1, 1));
+      if (tap + 1 < 9) ldm(am[1], tap + 1, 1);
       else if (PC && HID == 1) ldp(pl, 1);
       __builtin_amdgcn_sched_barrier(0);
       cross_pair(toff, 2);
@@ -760,15 +733,7 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
         const u32x4 ph = {pack2(hi[0], hi[1]), pack2(hi[2], hi[3]), pack2(hi[4], hi[5]), pack2(hi[6], hi[7])};
         const u32x4 pl = {pack2(v[0] - hi[0], v[1] - hi[1]), pack2(v[2] - hi[2], v[3] - hi[3]),
                           pack2(v[4] - hi[4], v[5] - hi[5]), pack2(v[6] - hi[6], v[7] - hi[7])};
-#ifdef CF_MX_ARM_NOCVT   // dev timing arm (garbage results): the accumulator bits as operands, no bias / ReLU / split arithmetic
-        const bf16x8 xh = __builtin_bit_cast(bf16x8, u32x4{__builtin_bit_cast(unsigned, acc[2 * s2][ct][0]), __builtin_bit_cast(unsigned, acc[2 * s2][ct][1]),
-                                                           __builtin_bit_cast(unsigned, acc[2 * s2][ct][2]), __builtin_bit_cast(unsigned, acc[2 * s2][ct][3])});
-        const bf16x8 xl = __builtin_bit_cast(bf16x8, u32x4{__builtin_bit_cast(unsigned, acc[2 * s2 + 1][ct][0]), __builtin_bit_cast(unsigned, acc[2 * s2 + 1][ct][1]),
-                                                           __builtin_bit_cast(unsigned, acc[2 * s2 + 1][ct][2]), __builtin_bit_cast(unsigned, acc[2 * s2 + 1][ct][3])});
-        (void)ph; (void)pl;
-#else
         const bf16x8 xh = __builtin_bit_cast(bf16x8, ph), xl = __builtin_bit_cast(bf16x8, pl);
-#endif
         oacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, xh, oacc[ct], 0, 0, 0);
         oacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xl, oacc[ct], 0, 0, 0);
         oacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xh, oacc[ct], 0, 0, 0);
@@ -776,15 +741,6 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
     }
   }
   const int n_out = p.n_out[head], act = p.act[head];
-#ifdef CF_MX_ARM_NORED     // dev timing arm (garbage results): no partial-sum exchange, no barriers, one store per lane
-  {
-    float sum = 0.0f;
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) sum += (oacc[ct][0] + oacc[ct][1]) + (oacc[ct][2] + oacc[ct][3]);
-    if (sum == 12345.0f) p.out[head][tid] = sum;
-  }
-  continue;
-#endif
   float* red = reinterpret_cast<float*>(xt + hp16_patch_bytes(PC) + hp16_pc_extra(PC));   // [wave][n 16][px 128], BEHIND the patch (which the next head reuses)
 #pragma unroll
   for (int ct = 0; ct < 8; ++ct)
@@ -908,8 +864,9 @@ constexpr int HEAD_MAX_K_PAD = 2048;   // bound of cf_head_fused_args.K_pad (64 
 #define CF_HEAD_FORMS "cf_head_fused runs layout3x3 = 1 (64-channel first source [, 8-channel second]) with mfma16 = 1 " \
                       "(16x16x32 fragments, n_out <= 16) only"
 
-// slot_pixels == nullptr: the dense launch over the whole map; else n_tiles virtual tiles (cf_head_fused_at)
-static int head_fused_launch(const cf_head_fused_args* a, const int* slot_pixels, int n_tiles, void* stream) {
+// slot_pixels == nullptr: the dense launch over the whole map; else n_tiles virtual tiles (cf_head_fused_at).
+// tile / pc_skip: 0 or 1 forces that choice, -1 leaves it to the rule (cf_head_fused_with)
+static int head_fused_launch(const cf_head_fused_args* a, const int* slot_pixels, int n_tiles, int tile, int pc_skip, void* stream) {
   const bool at = slot_pixels != nullptr;
   HeadPatchK hp{};
   hp.slot_pixels = slot_pixels;
@@ -960,24 +917,20 @@ static int head_fused_launch(const cf_head_fused_args* a, const int* slot_pixels
     CF_REQUIRE(a->tail.n_hidden > 0 || a->w_out_perm[i], "cf_head_fused: head %d: w_out_perm missing", i);
     hp.w_out_perm[i] = reinterpret_cast<const unsigned char*>(a->w_out_perm[i]);
   }
-  // tile orientation: 8 x 16 or 16 x 8 pixels, whichever covers the map with fewer tiles (results do not depend on it;
-  // CF_HEAD_TILE = 0 / 1 forces one for dev tools)
+  // tile orientation: 8 x 16 or 16 x 8 pixels, whichever covers the map with fewer tiles (results do not depend on it)
   const long t_land = (long)((W + 15) / 16) * ((H + 7) / 8), t_port = (long)((W + 7) / 8) * ((H + 15) / 16);
   CF_REQUIRE(t_land * a->tail.B * n_heads < (1L << 31), "cf_head_fused: grid too large");   // (bounds either orientation's grid)
   CF_REQUIRE(m16, CF_HEAD_FORMS ": nothing reads 32x32x16 fragments (mfma16 = 0)");
-  bool portrait = t_port < t_land;
-  if (const char* e = getenv("CF_HEAD_TILE")) portrait = atoi(e) != 0;
+  bool portrait = tile < 0 ? t_port < t_land : tile != 0;
   if (at) portrait = false;                  // (virtual tiles are flat)
-  // workgroups whose pc_hm patch is all zero leave the pc_hm taps out (results do not depend on it; CF_HEAD_PC_SKIP = 0
-  // runs them everywhere, for dev tools and tests)
-  hp.pc_skip = 1;
-  if (const char* e = getenv("CF_HEAD_PC_SKIP")) hp.pc_skip = atoi(e) != 0;
+  // workgroups whose pc_hm patch is all zero leave the pc_hm taps out (results do not depend on it)
+  hp.pc_skip = pc_skip != 0;
   hp.tiles_x = portrait ? (W + 7) / 8 : (W + 15) / 16;
   hp.tiles_y = portrait ? (H + 15) / 16 : (H + 7) / 8;
   const int n_img = at ? 1 : a->tail.B;      // virtual tiles are not per image: the table holds flat pixels of the batch
   if (at) { hp.tiles_x = n_tiles; hp.tiles_y = 1; }
-  // heads without hidden layers: a workgroup walks several heads on one patch (chosen below; CF_HEAD_LOOP overrides
-  // for dev tools).  With hidden layers the chain rewrites the patch: one head per workgroup.
+  // heads without hidden layers: a workgroup walks several heads on one patch (chosen below).  With hidden layers the
+  // chain rewrites the patch: one head per workgroup.
   int hloop = 1;
   if (a->tail.n_hidden == 0) {
     // heads per workgroup: 1, 2 or half of them, whichever needs the fewest rounds of (2 workgroups per CU) x (heads +
@@ -996,9 +949,6 @@ static int head_fused_launch(const cf_head_fused_args* a, const int* slot_pixels
       const double cost = (double)((tiles * ((n + h - 1) / h) + slots - 1) / slots) * (h + 0.25);
       if (i == 0 || cost < best - 1e-9) { best = cost; hloop = h; }
     }
-    if (const char* e = getenv("CF_HEAD_LOOP")) hloop = atoi(e);
-    if (hloop < 1) hloop = 1;
-    if (hloop > n) hloop = n;
   }
   hp.hloop = hloop;
   const long blocks = (long)hp.tiles_x * hp.tiles_y * n_img * ((n_heads + hloop - 1) / hloop);
@@ -1042,15 +992,19 @@ static int head_fused_launch(const cf_head_fused_args* a, const int* slot_pixels
   return cf_check_launch("cf_head_fused");
 }
 
-extern "C" int cf_head_fused(const cf_head_fused_args* a, void* stream) {
-  CF_REQUIRE(a != nullptr, "cf_head_fused: null args");
-  return head_fused_launch(a, nullptr, 0, stream);
+extern "C" int cf_head_fused_with(const cf_head_fused_args* a, int tile, int pc_skip, void* stream) {
+  CF_REQUIRE(a != nullptr, "cf_head_fused: null args (a)");
+  CF_REQUIRE(tile >= -1 && tile <= 1, "cf_head_fused_with: tile=%d is not 0 (8 x 16), 1 (16 x 8) or -1 (the rule's own)", tile);
+  CF_REQUIRE(pc_skip >= -1 && pc_skip <= 1, "cf_head_fused_with: pc_skip=%d is not 0, 1 or -1 (the rule's own)", pc_skip);
+  return head_fused_launch(a, nullptr, 0, tile, pc_skip, stream);
 }
+
+extern "C" int cf_head_fused(const cf_head_fused_args* a, void* stream) { return cf_head_fused_with(a, -1, -1, stream); }
 
 extern "C" int cf_head_fused_at(const cf_head_fused_args* a, const int32_t* slot_pixels, int n_tiles, void* stream) {
   CF_REQUIRE(a != nullptr, "cf_head_fused_at: null args");
   CF_REQUIRE(slot_pixels != nullptr && n_tiles > 0, "cf_head_fused_at: slot table missing or n_tiles=%d", n_tiles);
-  const int rc = head_fused_launch(a, slot_pixels, n_tiles, stream);
+  const int rc = head_fused_launch(a, slot_pixels, n_tiles, -1, -1, stream);
   if (rc == CF_EINVAL) {                     // (the shared checks name cf_head_fused: say which entry point was called)
     const std::string why = cf_last_error();
     cf_set_error("cf_head_fused_at: %s", why.c_str());

@@ -319,8 +319,13 @@ def pack_feat_mx(feat, out=None, scale=None):
     return out
 
 
-def run_head_fused(f):
-    _lib.check(_lib.load().cf_head_fused(C.byref(f), _lib.stream_ptr()), "cf_head_fused")
+def run_head_fused(f, tile=None, pc_skip=None):
+    """tile = 0 (8 x 16) / 1 (16 x 8), pc_skip = 0 / 1: force that choice of the launcher's (tests and measurement tools; the
+    bits depend on neither); None: the launcher's own."""
+    if tile is None and pc_skip is None:
+        return _lib.check(_lib.load().cf_head_fused(C.byref(f), _lib.stream_ptr()), "cf_head_fused")
+    force = lambda v: -1 if v is None else int(v)
+    _lib.check(_lib.load().cf_head_fused_with(C.byref(f), force(tile), force(pc_skip), _lib.stream_ptr()), "cf_head_fused_with")
 
 
 def dcn_args(pd: PackedDcn, x, offmask, om_stride, B, H, W, out, out_stride, act=ACT_RELU,

@@ -265,8 +265,8 @@ typedef struct cf_head_tail_args {
  * [256/16][K_pad/32] of head i in the canonical 3x3 slot order (packing.pack_conv_bf16); b_first[i]: 256 floats.
  * The pc_hm source (3 real channels) takes ONE k-step behind the 18 of the feature channels, k = 3 tap + channel (27 real,
  * k = 27..31 zero weights): the kernel gathers the matching operand rows from the pc_hm planes of its LDS patch.  A workgroup
- * whose pc_hm patch (tile + 1-pixel frame) holds only +-0 leaves that k-step out - it would add exact zeros; the environment
- * variable CF_HEAD_PC_SKIP = 0 runs it everywhere (dev switch, results are the same bits).  (layout of that k-step changed
+ * whose pc_hm patch (tile + 1-pixel frame) holds only +-0 leaves that k-step out - it would add exact zeros;
+ * cf_head_fused_with(a, -1, 0, stream) runs it everywhere (results are the same bits).  (layout of that k-step changed
  * within ABI 7: the argument block and the exports did not; w_first[] is whatever packing.py of the same tree writes)
  * ONE form runs: layout3x3 = 1 with mfma16 = 1 (mx = 0 or 1).  The fields can still spell the forms of earlier kernels
  * (layout3x3 = 0: an arbitrary slot table; mfma16 = 0: 32x32x16 fragments): those calls return CF_EINVAL. */
@@ -300,6 +300,10 @@ typedef struct cf_head_fused_args {
   float first_scale[CF_MAX_HEADS];         /* mx: 2^-(s+4) of head i's first layer (applied where b_first is added) */
 } cf_head_fused_args;
 int cf_head_fused(const cf_head_fused_args* a, void* stream);
+/* cf_head_fused with the launcher's two result-neutral choices forced: tile = 0 (8 x 16) / 1 (16 x 8) / -1 (the rule's own);
+   pc_skip = 0 / 1 / -1 likewise.  For tests and measurement tools; the bits do not depend on either.  Any other value is
+   CF_EINVAL, before any launch.  cf_head_fused(a, s) is cf_head_fused_with(a, -1, -1, s).  (added under ABI 7) */
+int cf_head_fused_with(const cf_head_fused_args* a, int tile, int pc_skip, void* stream);
 
 /* cf_head_fused_at: cf_head_fused at LISTED pixels only (no new struct, ABI 7): the same argument block, evaluated on n_tiles
  * "virtual tiles" of 18 pixels each.  slot_pixels: [n_tiles][18] int32 in device memory, each entry a flat pixel

@@ -98,6 +98,20 @@ def test_argument_validation_without_gpu():
     assert lib.cf_upsample_dw(None, None, None, None, 1, 1, 1, 4, 2, None) == -22
 
 
+def test_head_fused_with_validates_its_choices_without_gpu():
+    """cf_head_fused_with takes tile and pc_skip from {-1, 0, 1} only and refuses anything else, and a null block, with a
+    message that names the argument - before it reads the block (an all-zero one here) or reaches a launch."""
+    from centerfusiondetect3d_amd import _lib
+    lib = _lib.load()
+    f = _lib.HeadFusedArgs()
+    assert lib.cf_head_fused_with(ctypes.byref(f), 2, -1, None) == -22
+    assert b"cf_head_fused_with" in lib.cf_last_error() and b"tile=2" in lib.cf_last_error()
+    assert lib.cf_head_fused_with(ctypes.byref(f), 1, -2, None) == -22
+    assert b"cf_head_fused_with" in lib.cf_last_error() and b"pc_skip=-2" in lib.cf_last_error()
+    assert lib.cf_head_fused_with(None, 0, 0, None) == -22
+    assert b"null args (a)" in lib.cf_last_error()
+
+
 def test_frustum_map_bound_without_gpu():
     """The frustum kernel's ROI search divides by multiplication, exact while W * W * H < 2^32: both entry points refuse a
     larger map before they look at a pointer (all-null calls: nothing here can reach a launch)."""

@@ -101,18 +101,13 @@ def _heads_case(dev, n_hidden, radar, B, H, W, n_outs=(10, 1, 3, 8), acts=(2, 3,
     (1, True, 1, 8, 40),
 ])
 def test_head_fused_mx_whole_head(dev, n_hidden, radar, B, H, W):
-    import os
     from centerfusiondetect3d_amd import ops
     f, heads, refs64, refs32 = _heads_case(dev, n_hidden, radar, B, H, W)
     firsts = None
-    for tile in ("0", "1"):                                    # both tile orientations: identical bits
-        os.environ["CF_HEAD_TILE"] = tile
-        try:
-            for hd in heads:
-                hd["out"].fill_(float("nan"))
-            ops.run_head_fused(f)
-        finally:
-            del os.environ["CF_HEAD_TILE"]
+    for tile in (0, 1):                                        # both tile orientations: identical bits
+        for hd in heads:
+            hd["out"].fill_(float("nan"))
+        ops.run_head_fused(f, tile=tile)
         outs = [hd["out"].clone() for hd in heads] + [hd["out2"].clone() for hd in heads if hd["out2"] is not None]
         if firsts is None:
             firsts = outs

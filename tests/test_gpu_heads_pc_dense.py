@@ -12,9 +12,6 @@ Measured on the MI355X, worst head of each case, error vs float64 / vs fp32 (the
 brackets): mx (2, 2x13x19) 1.33e-5 / 2.19e-5 (1.42e-5 / 2.13e-5), mx (1, 1x8x40) 1.57e-5 / 1.68e-5 (1.56e-5 / 1.66e-5),
 mx (0, 1x21x37) 6.05e-6 / 8.82e-6 (6.05e-6 / 8.72e-6), bf16x3 (2, 2x13x19) 1.55e-5 / 1.53e-5 (the same), bf16x3 (0, 1x21x37)
 8.49e-6 / 8.52e-6 (the same); every head: docs/experiments/heads_pc_dense_ab.txt."""
-import contextlib
-import os
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -37,20 +34,6 @@ def rnd(*shape, seed=0, scale=1.0):
 
 def nhwc(x):
     return x.permute(0, 2, 3, 1).contiguous()
-
-
-@contextlib.contextmanager
-def env(**kv):
-    old = {k: os.environ.get(k) for k in kv}
-    os.environ.update({k: str(v) for k, v in kv.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
 
 
 def _weights(i, n_hidden, no):
@@ -94,7 +77,8 @@ def _inputs(B, H, W):
 
 
 def _launch(dev, mx, n_hidden, feat, pch):
-    """-> run(): launches the four heads on (feat, pch) and returns every output map (out of each head, then the out2 maps)"""
+    """-> run(tile=None, pc_skip=None): launches the four heads on (feat, pch), with that tile orientation / skip forced, and
+    returns every output map (out of each head, then the out2 maps)"""
     from centerfusiondetect3d_amd import ops
     B, _, H, W = feat.shape
     packed, slots, k_pad = _packed_heads(dev, mx, n_hidden)
@@ -106,12 +90,12 @@ def _launch(dev, mx, n_hidden, feat, pch):
     assert f.mx == int(mx) and f.mfma16 == 1 and f.layout3x3 == 1 and f.n_src == 2
     f._keep = srcs
 
-    def run():
+    def run(tile=None, pc_skip=None):
         for hd in heads:
             hd["out"].fill_(float("nan"))
             if hd["out2"] is not None:
                 hd["out2"].fill_(float("nan"))
-        ops.run_head_fused(f)
+        ops.run_head_fused(f, tile=tile, pc_skip=pc_skip)
         return [hd["out"].clone() for hd in heads] + [hd["out2"].clone() for hd in heads if hd["out2"] is not None]
     return run
 
@@ -147,10 +131,8 @@ def test_dense_pc_step_against_float64(dev, mx, n_hidden, B, H, W):
     """dense random pc_hm (x 20): every tile runs the radar k-step; both tile orientations give the same bits"""
     feat, pch = _inputs(B, H, W)
     run = _launch(dev, mx, n_hidden, feat, pch)
-    with env(CF_HEAD_TILE=0):
-        flat = run()
-    with env(CF_HEAD_TILE=1):
-        assert _same(flat, run())
+    flat = run(tile=0)
+    assert _same(flat, run(tile=1))
     outs = run()
     assert _same(flat, outs)
     out2 = iter(outs[len(N_OUTS):])
@@ -179,10 +161,8 @@ def _skip_on_off(run):
     """every output with the skip off and on, for both tile orientations: all equal; -> the outputs"""
     first = None
     for tile in (0, 1):
-        with env(CF_HEAD_TILE=tile, CF_HEAD_PC_SKIP=0):
-            off = run()
-        with env(CF_HEAD_TILE=tile):
-            on = run()
+        off = run(tile=tile, pc_skip=0)
+        on = run(tile=tile)
         assert _same(off, on), f"skip on != skip off (tile orientation {tile})"
         first = first or off
         assert _same(first, off)

@@ -559,14 +559,10 @@ def test_head_fused_whole_head(dev, n_hidden, radar, B, H, W, patch):
     # the 128-pixel tile lies flat (8 x 16) or stands upright (16 x 8), whichever needs fewer tiles: force both,
     # the results must not differ by a bit
     firsts = None
-    for tile in ("0", "1"):
-        os.environ["CF_HEAD_TILE"] = tile
-        try:
-            for hd in heads:
-                hd["out"].fill_(float("nan"))
-            ops.run_head_fused(f)
-        finally:
-            del os.environ["CF_HEAD_TILE"]
+    for tile in (0, 1):
+        for hd in heads:
+            hd["out"].fill_(float("nan"))
+        ops.run_head_fused(f, tile=tile)
         outs = [hd["out"].clone() for hd in heads] + [hd["out2"].clone() for hd in heads if hd["out2"] is not None]
         if firsts is None:
             firsts = outs
