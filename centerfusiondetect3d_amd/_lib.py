@@ -205,6 +205,9 @@ SYMBOLS = {
     "cf_radar_ingest": (_i, [_f, _f, _i, _i, _i, _f, _i, _i, _d, _d, _i, _f, _f, _f, _f]),
     "cf_preprocess_images": (_i, [_f, _i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_float),
                                  C.POINTER(C.c_float), _i, _i, _f, _f]),
+    "cf_augment_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "cf_augment_images": (_i, [_f, _i, _i, _i, _f, _f, _f, _f, _f, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _i, _f,
+                              _f, C.c_size_t, _f]),
     "cf_topk_workspace_bytes": (C.c_size_t, [_i, _i]),
     "cf_topk_workspace_bytes_nms": (C.c_size_t, [_i, _i, _i, _i, _i]),
     "cf_topk_peaks": (_i, [_f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f]),

@@ -35,6 +35,7 @@ SOURCES = [
     ("cf_frustum.hip", ["-ffp-contract=off"]),
     ("cf_decode.hip", ["-ffp-contract=off"]),
     ("cf_radar.hip", ["-ffp-contract=off"]),
+    ("cf_augment.hip", ["-ffp-contract=off"]),  # the fp32 colour chain rounds every operation, as torch's CPU kernels do
     ("cf_loss.hip", []),
     ("cf_targets.hip", ["-ffp-contract=off"]),
     ("cf_pack.cpp", ["-ffp-contract=off"]),     # host-side packers: the fp32 BN fold must round like torch's (no fused multiply-add)

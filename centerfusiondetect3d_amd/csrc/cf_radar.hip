@@ -2,6 +2,7 @@
 // (pillars / points / heatmap).  Float64 and fixed-point arithmetic written operation for operation like the reference's
 // (numpy, OpenCV); this file is compiled with -ffp-contract=off so no multiply-add is fused behind our back.
 #include "cf_common.h"
+#include "cf_warp_u8.h"
 
 namespace {
 constexpr int PL_THREADS = 256;
@@ -296,7 +297,7 @@ namespace {
 // border 0) of the uint8 camera frame in OpenCV's fixed-point arithmetic (10-bit coordinates, 5-bit
 // bilinear fractions, 15-bit weights: oracle/preprocess_ref.py states it), then
 // ((v / 255.0 - mean) / std) in float64 -> fp32, HWC -> CHW.  One thread per output pixel.
-// (This file is built with -ffp-contract=off: M1*y + M2 must round twice, as it does in OpenCV.)
+// (The warp itself is cf_warp_affine_u8, cf_warp_u8.h, shared with the training warp of cf_augment.hip.)
 // ---------------------------------------------------------------------------------------------
 struct PreK {
   const uint8_t* src;   // (B, Hs, Ws, 3)
@@ -312,27 +313,11 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreK p) {
     const int x = (int)(i % p.Wd);
     const long r = i / p.Wd;
     const int y = (int)(r % p.Hd), b = (int)(r / p.Hd);
-    const int X0 = __double2int_rn((p.m[1] * (double)y + p.m[2]) * 1024.0) + 16;
-    const int Y0 = __double2int_rn((p.m[4] * (double)y + p.m[5]) * 1024.0) + 16;
-    const int X = (X0 + __double2int_rn(p.m[0] * (double)x * 1024.0)) >> 5;
-    const int Y = (Y0 + __double2int_rn(p.m[3] * (double)x * 1024.0)) >> 5;
-    const int sx = X >> 5, sy = Y >> 5, fx = X & 31, fy = Y & 31;
-    const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32;
-    const int w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
-    const uint8_t* img = p.src + (size_t)b * p.Hs * p.Ws * 3;
-    const bool y0 = (unsigned)sy < (unsigned)p.Hs, y1 = (unsigned)(sy + 1) < (unsigned)p.Hs;
-    const bool x0 = (unsigned)sx < (unsigned)p.Ws, x1 = (unsigned)(sx + 1) < (unsigned)p.Ws;
-    const uint8_t* p00 = img + ((size_t)(y0 ? sy : 0) * p.Ws + (x0 ? sx : 0)) * 3;
-    const uint8_t* p01 = img + ((size_t)(y0 ? sy : 0) * p.Ws + (x1 ? sx + 1 : 0)) * 3;
-    const uint8_t* p10 = img + ((size_t)(y1 ? sy + 1 : 0) * p.Ws + (x0 ? sx : 0)) * 3;
-    const uint8_t* p11 = img + ((size_t)(y1 ? sy + 1 : 0) * p.Ws + (x1 ? sx + 1 : 0)) * 3;
-    const int m00 = (y0 && x0) ? w00 : 0, m01 = (y0 && x1) ? w01 : 0;
-    const int m10 = (y1 && x0) ? w10 : 0, m11 = (y1 && x1) ? w11 : 0;
+    int v[3];
+    cf_warp_affine_u8(p.src + (size_t)b * p.Hs * p.Ws * 3, p.Hs, p.Ws, p.m, x, y, false, v);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const int acc = p00[c] * m00 + p01[c] * m01 + p10[c] * m10 + p11[c] * m11;
-      const int v = (acc + (1 << 14)) >> 15;
-      const double n = ((double)v / 255.0 - p.mean[c]) / p.stdv[c];
+      const double n = ((double)v[c] / 255.0 - p.mean[c]) / p.stdv[c];
       p.out[(((size_t)b * 3 + c) * p.Hd + y) * p.Wd + x] = (float)n;
     }
   }

@@ -2,7 +2,7 @@
 
   getPcFrustumHeatmap(output, pc_dep, calib, config)  <- utils/pointcloud.py:331-394
   process_point_cloud_batch(...)                       <- dataset/generic_dataset.py:738-828 (all three PC_ROI_METHODs)
-  getAffineTransform(center, scale, 0, out_wh)         <- utils/image.py:43-83 (host, 3-point solve)
+  getAffineTransform(center, scale, rotation, out_wh)  <- utils/image.py:21-83 (host, 3-point solve)
 """
 import numpy as np
 import torch
@@ -20,16 +20,25 @@ def getPcFrustumHeatmap(output, pc_dep, calib, config):
 
 
 def getAffineTransform(center, scale, rotateFactor, outputSize):
-    """Source-image -> output-map affine for rotation 0 (the inference path, detector.py:206-221)."""
-    if rotateFactor != 0:
-        raise NotImplementedError("rotation augmentation is training-only")
-    src_w = np.float32(scale)
+    """Source-image -> output-map affine (utils/image.py:43-83): rotation 0 is the inference path (detector.py:206-221), a
+    rotation in degrees (`getDirection`, image.py:21-40) and a two-element scale (of which, as upstream, only the first element
+    enters) are the training augmentation's."""
+    if isinstance(scale, (np.ndarray, list, tuple)):
+        src_w = scale[0]
+    else:
+        src_w = np.float32(scale)
     dst_w, dst_h = outputSize
     center = np.asarray(center, np.float32)
     src = np.zeros((3, 2), np.float32)
     dst = np.zeros((3, 2), np.float32)
     src[0] = center
-    src[1] = center + np.array([0, src_w * -0.5], np.float32)
+    if rotateFactor != 0:
+        rad = np.pi * rotateFactor / 180.0
+        sin, cos, py = np.sin(rad), np.cos(rad), src_w * -0.5
+        direction = np.array([0 * cos - py * sin, 0 * sin + py * cos], np.float32)
+    else:
+        direction = np.array([0, src_w * -0.5], np.float32)
+    src[1] = center + direction
     dst[0] = np.array([dst_w * 0.5, dst_h * 0.5], np.float32)
     dst[1] = dst[0] + np.array([0, dst_w * -0.5], np.float32)
     for p in (src, dst):
@@ -67,7 +76,8 @@ def process_point_cloud_batch(pc_2d_list, pc_3d_list, calibs, trans_out, out_hw,
 
 
 def radar_to_pc_dep(radar_pcs, intrinsics, img_wh, calibs, trans_out, out_hw, max_dist=60.0, z_offset=0.0,
-                    pillar_dims=(1.5, 0.2, 0.2), descending=False, device="cuda", max_points=1024, roi_method="pillars"):
+                    pillar_dims=(1.5, 0.2, 0.2), descending=False, device="cuda", max_points=1024, roi_method="pillars",
+                    flip=None):
     """Whole radar side of `Detector.pre_process` on the device (detector.py:257-292): raw per-frame
     sweeps (R x N float64 arrays as unpickled from annotations/radar_pc/<sensor>/<token>.bin, rows
     0..2 = x, y, z in the camera frame) -> depth gate, z offset, image projection + border gate, depth
@@ -75,7 +85,10 @@ def radar_to_pc_dep(radar_pcs, intrinsics, img_wh, calibs, trans_out, out_hw, ma
     points cross PCIe; nothing is filtered, projected or sorted on the host.
     roi_method = DATASET.PC_ROI_METHOD (generic_dataset.py:774-826): "pillars", or "points" / "heatmap" (cf_radar_roi_expand);
     anything else raises ValueError before the device is touched.  The sort is the detector's for every method (ascending:
-    detector.py:280-283 does not look at PC_REVERSE, which only the dataset loader reads)."""
+    detector.py:280-283 does not look at PC_REVERSE, which only the dataset loader reads).
+    flip: None, or a per-frame mask (B) of frames whose image is mirrored (the training loader's isFlipped, nuscenes.py:201-205):
+    after the sort and before the expansion their points get u = img_w - 1 - u and rows 0 and 8 of pc_3d (x and the x velocity)
+    negated, in the ingest's float64, on the device and without a host synchronisation.  `trans_out` may be (2,3) or (B,2,3)."""
     ops.roi_method_id(roi_method)
     B = len(radar_pcs)
     arrs = [np.asarray(p, np.float64) for p in radar_pcs]
@@ -89,6 +102,18 @@ def radar_to_pc_dep(radar_pcs, intrinsics, img_wh, calibs, trans_out, out_hw, ma
     K = np.ascontiguousarray(np.broadcast_to(np.asarray(intrinsics, np.float64).reshape(-1, 3, 3), (B, 3, 3)))
     t = lambda a: torch.from_numpy(np.array(a, copy=True, order="C")).to(device)        # (a private, writable copy: torch refuses read-only arrays with a warning)
     pc_2d, pc_3d, counts = ops.radar_ingest(t(pc), t(cnt), t(K), img_wh, max_dist, z_offset, descending)
+    if flip is not None:
+        flip = torch.as_tensor(flip)
+        if tuple(flip.shape) != (B,):
+            raise ValueError(f"radar_to_pc_dep: flip must have shape ({B},), got {tuple(flip.shape)}")
+        live = torch.arange(max_n, device=pc_2d.device)[None, :] < counts[:, None]          # (the padding stays zero)
+        m = (flip.to(pc_2d.device, non_blocking=True) != 0)[:, None] & live
+        pc_2d[:, 0] = torch.where(m, (int(img_wh[0]) - 1) - pc_2d[:, 0], pc_2d[:, 0])
+        for r in (0, 8):
+            pc_3d[:, r] = torch.where(m, pc_3d[:, r] * -1, pc_3d[:, r])
     calibs = np.asarray(calibs, np.float64).reshape(B, 3, 4)
-    trans = np.broadcast_to(np.asarray(trans_out, np.float64), (B, 2, 3)).copy()
-    return _expand(pc_2d, pc_3d, counts, t(calibs), t(trans), out_hw, pillar_dims, roi_method)
+    if torch.is_tensor(trans_out):                                      # (AugmentParams.trans_out, possibly on the device already)
+        trans = trans_out.to(pc_2d.device, torch.float64, non_blocking=True).expand(B, 2, 3).contiguous()
+    else:
+        trans = t(np.broadcast_to(np.asarray(trans_out, np.float64), (B, 2, 3)))
+    return _expand(pc_2d, pc_3d, counts, t(calibs), trans, out_hw, pillar_dims, roi_method)

@@ -7,9 +7,10 @@
     outputs = model(images, pc_hm=batch["pc_hm"], pc_dep=pc_dep, calib=calib)     # model.train() on a frozen trunk
     total, losses = GenericLoss(config, 10)(outputs, batch)
 
-The caller still does what comes before the annotation loop: image loading, `getAugmentParam` and the two affine matrices
-(`trans_out` is `getAffineTransform(center, scale, rotation, [out_w, out_h])`, augmentation included), `flipAnnotations` on the
-dicts before they are packed, colour augmentation, lidar points and `prev` frames.
+What comes before the annotation loop is train_inputs.py: `draw_augmentation` (getAugmentParam, the flip draw and the two affine
+matrices: `trans_out` is its `getAffineTransform(center, scale, rotation, [out_w, out_h])`), `flip_annotations` on the dicts before
+they are packed, `augment_images` (warp, flip, colour augmentation) and `radar_to_pc_dep(flip=...)`.  The caller still loads the
+image bytes, the radar sweeps and the annotation dicts, and does lidar points and `prev` frames.
 """
 import ctypes
 

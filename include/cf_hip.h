@@ -464,6 +464,30 @@ int cf_radar_ingest(const double* pc, const int32_t* counts_in, int B, int n_row
 int cf_preprocess_images(const uint8_t* src, int B, int Hs, int Ws, const double* map_dst_to_src,
                          const float* mean, const float* stdv, int Hd, int Wd, float* out, void* stream);
 
+/* cf_augment_images: the image side of a TRAINING item (dataset/generic_dataset.py:159-190, 414-439): per frame
+ *   1. v = the 8-bit cv2.warpAffine(INTER_LINEAR, border 0) of cf_preprocess_images, with frame b's own dst -> src map; with
+ *      flip[b] != 0 the source is read as img[:, ::-1, :] (the tap column j is fetched from stored column Ws-1-j; coordinates,
+ *      weights and the validity test are unchanged);
+ *   2. t = (float)v / 255.0f;
+ *   3. if `colour`: for k in order[b] (0 brightness, 1 contrast, 2 saturation: the reference's ColorJitter list), with
+ *      r = factor[b][k], q = (float)(1.0 - (double)r), blend(a, o) = clamp(r*a + q*o, 0, 1) (mul, mul, add, each rounded):
+ *      brightness t = blend(t, 0); saturation t = blend(t, g), g = (0.2989f*t0 + 0.587f*t1) + 0.114f*t2 of this pixel (the
+ *      channels in stored order, no reordering: cv2.imread leaves BGR and ToTensor keeps it); contrast t = blend(t, m), m = the
+ *      mean of g over all Hd*Wd pixels of the frame as they stand at that point (border zeros included), summed in float64 in
+ *      a fixed order and rounded once to fp32.  Then t += lighting[b][c], unclamped;
+ *   4. out = (t - mean[c]) / std[c] in fp32 (the dataset's fp32 path, not cf_preprocess_images' float64 one).
+ * src (B,Hs,Ws,3) uint8, map_dst_to_src (B,6) f64, flip (B) u8 (a torch.bool tensor), order (B,3) i32, factor (B,3) f32, lighting (B,3) f32: DEVICE;
+ * order / factor / lighting may be NULL without `colour`.  mean, stdv: HOST pointers, three floats.  out (B,3,Hd,Wd) f32.
+ * With `colour` the caller hands in cf_augment_workspace_bytes(B, Hd, Wd) bytes of device memory, 8-byte aligned (per-block
+ * partial sums and the warped bytes); without it workspace may be NULL.  Two launches with colour, one without; no allocation,
+ * no host synchronisation, no atomics: the same input gives the same bits on every run and in every batch.
+ * Limits (refused with CF_EINVAL): every size < 32768, B * ceil(Hd*Wd / 1024) <= 2^31 - 1, std[c] != 0.  An `order` entry
+ * outside 0..2 is skipped (the Python side validates the table on the host). */
+size_t cf_augment_workspace_bytes(int B, int Hd, int Wd);
+int cf_augment_images(const uint8_t* src, int B, int Hs, int Ws, const double* map_dst_to_src, const uint8_t* flip,
+                      const int32_t* order, const float* factor, const float* lighting, const float* mean, const float* stdv,
+                      int colour, int Hd, int Wd, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* cf_topk_peaks: per-image top-K over a (B,C,H,W) NCHW score map, optionally after the 3x3
  * equality NMS, ordered by (score desc, class asc, pixel asc).
  * replaces model/utils.py:6-38 (topk) [+ model/utils.py:112-128 (nms) when nms != 0].
