@@ -211,6 +211,8 @@ SYMBOLS = {
     "cf_topk_workspace_bytes": (C.c_size_t, [_i, _i]),
     "cf_topk_workspace_bytes_nms": (C.c_size_t, [_i, _i, _i, _i, _i]),
     "cf_topk_peaks": (_i, [_f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f]),
+    "cf_topk_peaks_fused_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "cf_topk_peaks_fused": (_i, [_f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "cf_topk_peaks_if_changed": (_i, [_f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f]),
     "cf_checksum64": (_i, [_f, C.c_long, _f, _f]),
     "cf_frustum_assoc": (_i, [_f, _i, _f, _f, _f, _f, _f, _f, _i, _i, _i, C.c_float, _f, _f, _f, _f]),

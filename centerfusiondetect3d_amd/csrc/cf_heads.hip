@@ -70,7 +70,8 @@ __device__ __forceinline__ const bf16x8* wfrag(const unsigned char* w, int rt, i
 
 // 16x16 accumulators of one 64-pixel half tile (v_mfma_f32_16x16x32_bf16: lane = pixel ct*16 + (l & 15), reg r = channel
 // 64w + 16rt + 4(l >> 4) + r) -> ReLU(acc + b) -> split bf16 -> LDS tile [plane][px][528 B]
-template <bool SCALED = false>
+// CTS: bit ct set = column tile ct (16 pixels) is stored (default: all four; the AT kernels keep the tile rows with a centre)
+template <bool SCALED = false, int CTS = 0xF>
 __device__ __forceinline__ void store_hidden_tile16(unsigned char* xt, const f32x4 (&acc)[4][4], const float* bias,
                                                     int wave, int lane, float sc = 1.0f, int pxcol = -1) {
   const int g = lane >> 4, c16 = pxcol < 0 ? (lane & 15) : pxcol;   // pxcol: the pixel column this lane's accumulators hold
@@ -80,6 +81,7 @@ __device__ __forceinline__ void store_hidden_tile16(unsigned char* xt, const f32
     const f32x4 bb = *reinterpret_cast<const f32x4*>(bias + ch);
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) {
+      if (!((CTS >> ct) & 1)) continue;
       float v[4], hi[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -109,7 +111,7 @@ struct TileMap {       // 64 pixels of a tile at (y0, x0) of image b: 4 rows of 
 
 // Virtual tiles (head_patch16_kernel<.., AT>): the 8 x 16 tile holds 3 x 6 disjoint 3x3 neighbourhoods whose centres - tile pixels
 // (row 0 / 3 / 6, column 0 / 3 / .. / 15) - are the slots of a per-tile table of flat map pixels b * HW + y * W + x (-1: empty)
-constexpr int AT_SLOTS = 18;
+constexpr int AT_SLOTS = CF_HEAD_AT_SLOTS;
 __device__ __forceinline__ int at_slot_of(int ty, int tx) { return (ty % 3 == 0 && tx % 3 == 0) ? (ty / 3) * 6 + tx / 3 : -1; }
 struct SlotMap {       // 64 pixels of one half of a virtual tile: only the centres of non-empty slots are written
   const int* slots;
@@ -128,7 +130,8 @@ struct SlotMap {       // 64 pixels of one half of a virtual tile: only the cent
 // Hidden layers + output layer on a pixel tile that is already in LDS (xt).  All 256 threads.  Weights packed by
 // pack_fragments16: w_hidden [16 rt][8 ks], w_out one 16-row tile; wave w owns channels [64w, 64w+64) x 64 pixels as
 // 4 x 4 accumulators of 16 x 16; a k-step is 32 deep.
-template <class PixMap>
+// CTS: the column tiles (bit ct) that are computed and whose pixels pm may accept (default: all four)
+template <class PixMap, int CTS = 0xF>
 __device__ __forceinline__ void head_tail_from_lds16(const HeadTailK& p, unsigned char* xt, int head, const PixMap& pm) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, c16 = lane & 15;
@@ -160,6 +163,7 @@ __device__ __forceinline__ void head_tail_from_lds16(const HeadTailK& p, unsigne
       bf16x8 xh[4], xl[4];
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
+        if (!((CTS >> ct) & 1)) continue;
         const unsigned char* row = xt + (ct * 16 + c16) * HT_ROWB + (ks * 32 + g * 8) * 2;
         xh[ct] = *reinterpret_cast<const bf16x8*>(row);
         xl[ct] = *reinterpret_cast<const bf16x8*>(row + HT_PLANE);
@@ -168,21 +172,21 @@ __device__ __forceinline__ void head_tail_from_lds16(const HeadTailK& p, unsigne
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
-          acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[ks & 1][rt], xh[ct], acc[rt][ct], 0, 0, 0);
+          if ((CTS >> ct) & 1) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[ks & 1][rt], xh[ct], acc[rt][ct], 0, 0, 0);
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
-          acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks & 1][rt], xl[ct], acc[rt][ct], 0, 0, 0);
+          if ((CTS >> ct) & 1) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks & 1][rt], xl[ct], acc[rt][ct], 0, 0, 0);
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
-          acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks & 1][rt], xh[ct], acc[rt][ct], 0, 0, 0);
+          if ((CTS >> ct) & 1) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks & 1][rt], xh[ct], acc[rt][ct], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();  // every wave has read the whole tile: rewrite it in place
-    store_hidden_tile16(xt, acc, bias, wave, lane);
+    store_hidden_tile16<false, CTS>(xt, acc, bias, wave, lane);
     __syncthreads();
   }
 
@@ -200,6 +204,7 @@ __device__ __forceinline__ void head_tail_from_lds16(const HeadTailK& p, unsigne
       const bf16x8 ah = *wfrag(w, 0, ks, 0, 8, lane), al = *wfrag(w, 0, ks, 1, 8, lane);
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
+        if (!((CTS >> ct) & 1)) continue;
         const unsigned char* row = xt + (ct * 16 + c16) * HT_ROWB + (ks * 32 + g * 8) * 2;
         const bf16x8 xh = *reinterpret_cast<const bf16x8*>(row);
         const bf16x8 xl = *reinterpret_cast<const bf16x8*>(row + HT_PLANE);
@@ -217,7 +222,7 @@ __device__ __forceinline__ void head_tail_from_lds16(const HeadTailK& p, unsigne
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int n = 4 * g + r;
-      if (n < n_out) red[(wave * 16 + n) * HT_PX + ct * 16 + c16] = oacc[ct][r];
+      if (((CTS >> ct) & 1) && n < n_out) red[(wave * 16 + n) * HT_PX + ct * 16 + c16] = oacc[ct][r];
     }
   __syncthreads();
   const float* bo = p.b_out[head];
@@ -344,6 +349,10 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
   // AT: this workgroup's slots; patch row (pr, pc) of the 10 x 18 patch is neighbour (pr % 3 - 1, pc % 3 - 1) of slot (pr / 3, pc / 3)
   // -> its flat map pixel, or -1 = a zero row (outside the image, an empty slot, the unused 10th patch row)
   const int* const at_slots = AT ? q.slot_pixels + (size_t)rem * AT_SLOTS : nullptr;
+  // AT: on the flat tile a column tile ct is tile ROW ct, and only rows 0, 3 and 6 hold a centre (at_slot_of): every loop over
+  // column tiles below leaves the other five out - at compile time, inside the unrolled loops, so their accumulators and
+  // fragment reads do not exist.  (MFMA accumulator columns are independent: a written pixel keeps its bits.)
+  constexpr auto live = [](int ct) { return !AT || ct % 3 == 0; };
   auto at_src = [&](int row) -> int {
     const int pr = row / P_W, pc = row % P_W;
     if (pr >= 9) return -1;
@@ -480,6 +489,7 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       bf16x8 xh[4], xl[4];
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
+        if (!live(4 * hf + ct)) continue;
         const unsigned char* r = pcimg + imgb + (4 * hf + ct) * (16 * 2 * HP_PCIMG_ROWB);
         xh[ct] = *reinterpret_cast<const bf16x8*>(r);
         xl[ct] = *reinterpret_cast<const bf16x8*>(r + HP_PCIMG_ROWB);
@@ -488,17 +498,20 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
-          acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[rt], xh[ct], acc[rt][4 * hf + ct], 0, 0, 0);
+          if (live(4 * hf + ct))
+            acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[rt], xh[ct], acc[rt][4 * hf + ct], 0, 0, 0);
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
-          acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt], xl[ct], acc[rt][4 * hf + ct], 0, 0, 0);
+          if (live(4 * hf + ct))
+            acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt], xl[ct], acc[rt][4 * hf + ct], 0, 0, 0);
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
-          acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt], xh[ct], acc[rt][4 * hf + ct], 0, 0, 0);
+          if (live(4 * hf + ct))
+            acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt], xh[ct], acc[rt][4 * hf + ct], 0, 0, 0);
     }
   };
   auto first_layer = [&](int head, f32x4 (&acc)[4][8]) __attribute__((always_inline)) {
@@ -555,18 +568,21 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
     auto main_half = [&](const hf16x8 (&A)[4], int off, int hf) {
       hf16x8 xb[4];
 #pragma unroll
-      for (int ct = 0; ct < 4; ++ct) xb[ct] = *reinterpret_cast<const hf16x8*>(xt + rowb[4 * hf + ct] + off);
+      for (int ct = 0; ct < 4; ++ct)
+        if (live(4 * hf + ct)) xb[ct] = *reinterpret_cast<const hf16x8*>(xt + rowb[4 * hf + ct] + off);
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
-          acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[rt], xb[ct], acc[rt][4 * hf + ct], 0, 0, 0);
+          if (live(4 * hf + ct))
+            acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[rt], xb[ct], acc[rt][4 * hf + ct], 0, 0, 0);
     };
     auto cross_pair = [&](int toff, int pr) {
       i32x8 xb[2];
       int sb[2];
 #pragma unroll
       for (int c2 = 0; c2 < 2; ++c2) {
+        if (!live(2 * pr + c2)) continue;                  // (AT: pair 2 goes entirely, pairs 0, 1 and 3 keep one tile row each)
         const unsigned char* r = xt + rowb[2 * pr + c2] + toff;
         const u32x4 b0 = *reinterpret_cast<const u32x4*>(r + 64 * g + 32);
         const u32x2 b1 = *reinterpret_cast<const u32x2*>(r + 64 * g + 48);
@@ -577,7 +593,7 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       {                                                                                                                 \
         const i32x8 a6 = {(int)ax0[RT][0], (int)ax0[RT][1], (int)ax0[RT][2], (int)ax0[RT][3], (int)ax1[RT][0],          \
                           (int)ax1[RT][1], 0, 0};                                                                       \
-        _Pragma("unroll") for (int c2 = 0; c2 < 2; ++c2)                                                                \
+        _Pragma("unroll") for (int c2 = 0; c2 < 2; ++c2) if (live(2 * pr + c2))                                         \
           acc[RT][2 * pr + c2] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a6, xb[c2], acc[RT][2 * pr + c2],    \
                                                                                   2, 2, RT, sa, 0, sb[c2]);             \
       }
@@ -650,6 +666,7 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       bf16x8 xh[4], xl[4];
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
+        if (!live(4 * hf + ct)) continue;
         xh[ct] = *reinterpret_cast<const bf16x8*>(xt + rowb[4 * hf + ct] + off);
         xl[ct] = *reinterpret_cast<const bf16x8*>(xt + rowb[4 * hf + ct] + off + lo);
       }
@@ -657,17 +674,20 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
-          acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[ks & 1][rt], xh[ct], acc[rt][4 * hf + ct], 0, 0, 0);
+          if (live(4 * hf + ct))
+            acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[ks & 1][rt], xh[ct], acc[rt][4 * hf + ct], 0, 0, 0);
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
-          acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks & 1][rt], xl[ct], acc[rt][4 * hf + ct], 0, 0, 0);
+          if (live(4 * hf + ct))
+            acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks & 1][rt], xl[ct], acc[rt][4 * hf + ct], 0, 0, 0);
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
-          acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks & 1][rt], xh[ct], acc[rt][4 * hf + ct], 0, 0, 0);
+          if (live(4 * hf + ct))
+            acc[rt][4 * hf + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks & 1][rt], xh[ct], acc[rt][4 * hf + ct], 0, 0, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -690,10 +710,18 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) a2[rt][ct] = acc[rt][4 * half + ct];
+      // AT: the tile rows with a centre - 0 and 3 of half 0, 6 (local 2) of half 1; the chain's other rows are neither written nor read
+      if constexpr (AT) {
+        if (half == 0) store_hidden_tile16<MX, 0x9>(xt, a2, q.b_first[head], wave, lane, MX ? q.first_scale[head] : 1.0f, c16);
+        else store_hidden_tile16<MX, 0x4>(xt, a2, q.b_first[head], wave, lane, MX ? q.first_scale[head] : 1.0f, c16);
+      } else
       store_hidden_tile16<MX>(xt, a2, q.b_first[head], wave, lane, MX ? q.first_scale[head] : 1.0f, c16);
       if constexpr (MX) __builtin_amdgcn_sched_barrier(0);     // (the chain's first weight loads stay behind the tile stores)
       __syncthreads();
-      if constexpr (AT) head_tail_from_lds16(p, xt, head, SlotMap{at_slots, p.M, p.HW, half});
+      if constexpr (AT) {
+        if (half == 0) head_tail_from_lds16<SlotMap, 0x9>(p, xt, head, SlotMap{at_slots, p.M, p.HW, half});
+        else head_tail_from_lds16<SlotMap, 0x4>(p, xt, head, SlotMap{at_slots, p.M, p.HW, half});
+      }
       else head_tail_from_lds16(p, xt, head, TileMap{b, y0 + (64 >> TSH) * half, x0, q.H, q.W, TSH});
       __syncthreads();
     }
@@ -723,6 +751,7 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
       const f32x4 bb = *reinterpret_cast<const f32x4*>(b1 + 32 * s2 + 16);
 #pragma unroll
       for (int ct = 0; ct < 8; ++ct) {
+        if (!live(ct)) continue;
         float v[8], hi[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -747,7 +776,7 @@ __global__ __launch_bounds__(256, 2) void head_patch16_kernel(HeadPatchK q) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int n = 4 * g + r;
-      if (n < n_out) red[(wave * 16 + n) * HP_PX + ct * 16 + c16] = oacc[ct][r];
+      if (live(ct) && n < n_out) red[(wave * 16 + n) * HP_PX + ct * 16 + c16] = oacc[ct][r];
     }
   __syncthreads();
   {

@@ -180,33 +180,27 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_slice_kernel(const float* _
 // same keys: A. lower bound L = the K-th largest of G GROUP maxima (a group = 1024 / G neighbouring threads: G >= K distinct
 // elements, so at least K elements are >= L); B. everything above L into LDS - from the registers; ties / plateaus and the
 // adversarial case exactly as above, on the registers; C. rank counting.
-__global__ __launch_bounds__(TOPK_RT) void topk_slice_reg_kernel(const float* __restrict__ heat, int C, int H, int W, int K,
-                                                                 uint64_t* __restrict__ out_keys) {
-  __shared__ uint64_t keys[TOPK_CAP];
-  __shared__ __attribute__((aligned(16))) uint32_t gmax[256];
-  __shared__ uint32_t hist[256];
-  __shared__ uint32_t wave_cnt[TOPK_RT / 64];
-  __shared__ uint32_t s_gt, s_sel[2];
+// the LDS of a register-cached slice workgroup (one per kernel: the fused kernel's two selections run on the same one)
+struct TopkRegLds {
+  uint64_t keys[TOPK_CAP];
+  __attribute__((aligned(16))) uint32_t gmax[256];
+  uint32_t hist[256];
+  uint32_t wave_cnt[TOPK_RT / 64];
+  uint32_t s_gt, s_sel[2];
+};
+
+// steps A - C on the registers: u[e] = the order-preserving score of flat element lo + tid + e * TOPK_RT (0 past `hi`) of a
+// slice of more than K elements -> its K largest as sorted keys in out[0 .. K).  Whole workgroup of TOPK_RT threads.
+__device__ __forceinline__ void topk_reg_select(TopkRegLds& s, const uint32_t (&u)[TOPK_RE], int lo, int hi, int K,
+                                                uint64_t* __restrict__ out) {
+  uint64_t* const keys = s.keys;
+  uint32_t* const gmax = s.gmax;
+  uint32_t* const hist = s.hist;
+  uint32_t* const wave_cnt = s.wave_cnt;
+  uint32_t& s_gt = s.s_gt;
+  uint32_t* const s_sel = s.s_sel;
   const int tid = threadIdx.x;
-  const int N = C * H * W;
-  const int img_i = blockIdx.x / TOPK_SLICES, slice = blockIdx.x % TOPK_SLICES;
-  const float* img = heat + (size_t)img_i * N;
-  const int len = (N + TOPK_SLICES - 1) / TOPK_SLICES;
-  const int lo = min(slice * len, N), hi = min(lo + len, N);
-  uint64_t* out = out_keys + (size_t)blockIdx.x * K;
-  const int n = hi - lo;
-  if (n <= K) {
-    topk_tiny_slice<TOPK_RT>(keys, lo, n, K, out, [&](int i) { return f2u(img[i]); });
-    return;
-  }
-  // element e of this thread = lo + tid + e * TOPK_RT: for a fixed e the threads walk the slice in index order
-  uint32_t u[TOPK_RE];
   uint32_t lmax = 0;
-#pragma unroll
-  for (int e = 0; e < TOPK_RE; ++e) {
-    const int i = lo + tid + e * TOPK_RT;
-    u[e] = i < hi ? f2u(img[i]) : 0u;          // (0 ranks below every float but one NaN pattern; validity is tested by index)
-  }
 #pragma unroll
   for (int e = 0; e < TOPK_RE; ++e) lmax = max(lmax, u[e]);
   // ---- A: the K-th largest of the G group maxima (ties ranked by group id).  G = 128 groups of 8 neighbouring threads for
@@ -307,6 +301,94 @@ __global__ __launch_bounds__(TOPK_RT) void topk_slice_reg_kernel(const float* __
   rank_select_desc(keys, total, K, out);         // (total <= TOPK_CAP = 4 * TOPK_RT)
 }
 
+__global__ __launch_bounds__(TOPK_RT) void topk_slice_reg_kernel(const float* __restrict__ heat, int C, int H, int W, int K,
+                                                                 uint64_t* __restrict__ out_keys) {
+  __shared__ TopkRegLds s;
+  const int tid = threadIdx.x;
+  const int N = C * H * W;
+  const int img_i = blockIdx.x / TOPK_SLICES, slice = blockIdx.x % TOPK_SLICES;
+  const float* img = heat + (size_t)img_i * N;
+  const int len = (N + TOPK_SLICES - 1) / TOPK_SLICES;
+  const int lo = min(slice * len, N), hi = min(lo + len, N);
+  uint64_t* out = out_keys + (size_t)blockIdx.x * K;
+  const int n = hi - lo;
+  if (n <= K) {
+    topk_tiny_slice<TOPK_RT>(s.keys, lo, n, K, out, [&](int i) { return f2u(img[i]); });
+    return;
+  }
+  // element e of this thread = lo + tid + e * TOPK_RT: for a fixed e the threads walk the slice in index order
+  uint32_t u[TOPK_RE];
+#pragma unroll
+  for (int e = 0; e < TOPK_RE; ++e) {
+    const int i = lo + tid + e * TOPK_RT;
+    u[e] = i < hi ? f2u(img[i]) : 0u;          // (0 ranks below every float but one NaN pattern; validity is tested by index)
+  }
+  topk_reg_select(s, u, lo, hi, K, out);
+}
+
+// The register-cached form with the 3x3 equality NMS inside, and optionally BOTH lists from one read (cf_topk_peaks_fused: the
+// index pass of an at-peaks forward, which runs in line and alone on the chip - 1024-thread workgroups find their room).  An
+// element's NMS'd score is peak_value<true> of its position - what nms_kernel writes, so the keys are those of the two-pass
+// form - from nine loads at clamped window coordinates (at a border the clamp repeats a row / column of the window: the max
+// does not change), TOPK_NB elements = 36 loads in flight at a time (16 x 9 values do not fit the 128 registers of a
+// 1024-thread workgroup).  The centre value is the raw score.  RAW: the raw list is selected first, then - same LDS - the
+// NMS'd one; the slice lists of the raw set lie at out_keys, those of the NMS'd set `set_stride` keys behind.
+constexpr int TOPK_NB = 4;
+template <bool RAW>
+__global__ __launch_bounds__(TOPK_RT) void topk_slice_reg_nms_kernel(const float* __restrict__ heat, int C, int H, int W, int K,
+                                                                     uint64_t* __restrict__ out_keys, size_t set_stride) {
+  __shared__ TopkRegLds s;
+  const int tid = threadIdx.x;
+  const int HW = H * W, N = C * HW;
+  const int img_i = blockIdx.x / TOPK_SLICES, slice = blockIdx.x % TOPK_SLICES;
+  const float* img = heat + (size_t)img_i * N;
+  const int len = (N + TOPK_SLICES - 1) / TOPK_SLICES;
+  const int lo = min(slice * len, N), hi = min(lo + len, N);
+  uint64_t* out_raw = out_keys + (size_t)blockIdx.x * K;
+  uint64_t* out_nms = out_raw + set_stride;
+  const int n = hi - lo;
+  if (n <= K) {
+    if (RAW) {
+      topk_tiny_slice<TOPK_RT>(s.keys, lo, n, K, out_raw, [&](int i) { return f2u(img[i]); });
+      __syncthreads();                         // (the sorted keys are read out: the next sort rewrites them)
+    }
+    topk_tiny_slice<TOPK_RT>(s.keys, lo, n, K, out_nms, [&](int i) { return f2u(peak_value<true>(img, i, H, W)); });
+    return;
+  }
+  uint32_t ur[TOPK_RE], un[TOPK_RE];                  // (!RAW: ur is never read)
+#pragma unroll
+  for (int eb = 0; eb < TOPK_RE; eb += TOPK_NB) {
+    float w[TOPK_NB][9];
+#pragma unroll
+    for (int q = 0; q < TOPK_NB; ++q) {
+      const int i = min(lo + tid + (eb + q) * TOPK_RT, hi - 1);      // (past the slice: a valid address, the value is dropped)
+      const int c = i / HW, pix = i - c * HW;
+      const int y = pix / W, x = pix - y * W;
+      const float* pl = img + (size_t)c * HW;
+      const int r0 = (y > 0 ? y - 1 : y) * W, r1 = y * W, r2 = (y < H - 1 ? y + 1 : y) * W;
+      const int x0 = x > 0 ? x - 1 : x, x2 = x < W - 1 ? x + 1 : x;
+      w[q][0] = pl[r0 + x0]; w[q][1] = pl[r0 + x]; w[q][2] = pl[r0 + x2];
+      w[q][3] = pl[r1 + x0]; w[q][4] = pl[r1 + x]; w[q][5] = pl[r1 + x2];
+      w[q][6] = pl[r2 + x0]; w[q][7] = pl[r2 + x]; w[q][8] = pl[r2 + x2];
+    }
+#pragma unroll
+    for (int q = 0; q < TOPK_NB; ++q) {
+      const bool in = lo + tid + (eb + q) * TOPK_RT < hi;
+      const float v = w[q][4];
+      float m = v;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) m = fmaxf(m, w[q][k]);
+      un[eb + q] = in ? f2u((m == v) ? v : v * 0.0f) : 0u;
+      ur[eb + q] = in ? f2u(v) : 0u;
+    }
+  }
+  if constexpr (RAW) {
+    topk_reg_select(s, ur, lo, hi, K, out_raw);
+    __syncthreads();                           // (the last ranking pass reads the candidates: the next selection rewrites them)
+  }
+  topk_reg_select(s, un, lo, hi, K, out_nms);
+}
+
 // the K merged keys of image b -> scores / pixel / class (whole workgroup of THREADS)
 template <int THREADS>
 __device__ __forceinline__ void emit_peaks(const uint64_t* best, int K, int HW, int b, float* __restrict__ scores,
@@ -332,6 +414,55 @@ __global__ __launch_bounds__(TOPK_MERGE_THREADS) void topk_merge_kernel(const ui
   for (int i = tid; i < total; i += TOPK_MERGE_THREADS) keys[i] = src[i];
   __syncthreads();
   emit_peaks<TOPK_MERGE_THREADS>(merge_sorted_lists(keys, keys + total, K), K, HW, blockIdx.x, scores, inds, classes);
+}
+
+// Pass 2 of cf_topk_peaks_fused: grid = B x (the sets present), workgroup (b, set) merges the slice lists of image b of its
+// set (0 = raw: keys at in_keys, 1 = NMS'd: set_stride keys behind; raw.scores == nullptr: the NMS'd set alone) and emits
+// scores / pixel / class - and the entries of cf_head_fused_at's slot tables that come from its list, as
+// head_slot_tables_kernel (cf_heads.hip) writes them: tab_ab [B][ceil(2K / 18) * 18] = raw list | NMS'd list | -1,
+// tab_b [B][ceil(K / 18) * 18] = NMS'd list | -1, an entry = b * HW + pixel.  The NMS'd set's workgroup writes the padding
+// (and, without a raw set, -1 where the raw list would stand).
+struct TopkPeakOut {
+  float* scores;
+  int32_t* inds;
+  int32_t* classes;
+};
+__global__ __launch_bounds__(TOPK_MERGE_THREADS) void topk_merge_fused_kernel(const uint64_t* __restrict__ in_keys, size_t set_stride,
+                                                                              int B, int K, int HW, TopkPeakOut raw, TopkPeakOut nms,
+                                                                              int32_t* __restrict__ tab_ab, int32_t* __restrict__ tab_b) {
+  extern __shared__ __attribute__((aligned(16))) uint64_t keys[];      // topk_merge_lds_bytes(K)
+  const int tid = threadIdx.x, total = TOPK_SLICES * K;
+  const bool has_raw = raw.scores != nullptr;
+  const int b = blockIdx.x % B, set = has_raw ? blockIdx.x / B : 1;
+  const uint64_t* src = in_keys + (size_t)set * set_stride + (size_t)b * total;
+  for (int i = tid; i < total; i += TOPK_MERGE_THREADS) keys[i] = src[i];
+  __syncthreads();
+  const uint64_t* best = merge_sorted_lists(keys, keys + total, K);
+  const TopkPeakOut o = set ? nms : raw;
+  constexpr int slots = CF_HEAD_AT_SLOTS;
+  const int per_p = (2 * K + slots - 1) / slots * slots, per_s = (K + slots - 1) / slots * slots;
+  int32_t* const tp = tab_ab ? tab_ab + (size_t)b * per_p : nullptr;
+  int32_t* const ts = tab_b ? tab_b + (size_t)b * per_s : nullptr;
+  for (int j = tid; j < K; j += TOPK_MERGE_THREADS) {
+    float score;
+    int pix, cls;
+    unpack_key(best[j], HW, score, pix, cls);
+    o.scores[(size_t)b * K + j] = score;
+    o.inds[(size_t)b * K + j] = pix;
+    o.classes[(size_t)b * K + j] = cls;
+    const int v = (unsigned)pix < (unsigned)HW ? b * HW + pix : -1;
+    if (tp) tp[set * K + j] = v;
+    if (ts && set) ts[j] = v;
+  }
+  if (set) {
+    if (tp) {
+      for (int j = 2 * K + tid; j < per_p; j += TOPK_MERGE_THREADS) tp[j] = -1;
+      if (!has_raw)
+        for (int j = tid; j < K; j += TOPK_MERGE_THREADS) tp[j] = -1;
+    }
+    if (ts)
+      for (int j = K + tid; j < per_s; j += TOPK_MERGE_THREADS) ts[j] = -1;
+  }
 }
 }  // namespace
 
@@ -384,6 +515,47 @@ extern "C" int cf_topk_peaks(const float* heat, int B, int C, int H, int W, int 
   hipLaunchKernelGGL(topk_merge_kernel, dim3(B), dim3(TOPK_MERGE_THREADS), topk_merge_lds_bytes(K), st,
                      static_cast<const uint64_t*>(workspace), K, H * W, scores, inds, classes);
   return cf_check_launch("cf_topk_peaks");
+}
+
+// workspace of cf_topk_peaks_fused: [raw slice lists][NMS'd slice lists][long slices only: the suppressed map of the two-pass form]
+static bool topk_fused_reg(int C, int H, int W) {
+  return ((long)C * H * W + TOPK_SLICES - 1) / TOPK_SLICES <= (long)TOPK_RT * TOPK_RE;
+}
+
+extern "C" size_t cf_topk_peaks_fused_workspace_bytes(int B, int C, int H, int W, int K) {
+  const bool reg = C > 0 && H > 0 && W > 0 && topk_fused_reg(C, H, W);
+  return cf_topk_workspace_bytes(B, K) + (reg ? cf_topk_workspace_bytes(B, K) : cf_topk_workspace_bytes_nms(B, C, H, W, K));
+}
+
+extern "C" int cf_topk_peaks_fused(const float* heat, int B, int C, int H, int W, int K, float* raw_scores, int32_t* raw_inds,
+                                   int32_t* raw_classes, float* scores, int32_t* inds, int32_t* classes, int32_t* table_ab,
+                                   int32_t* table_b, void* workspace, void* stream) {
+  const char* who = "cf_topk_peaks_fused";
+  CF_REQUIRE(heat && scores && inds && classes && workspace, "%s: null buffer", who);
+  const bool raw = raw_scores != nullptr;
+  CF_REQUIRE(raw == (raw_inds != nullptr) && raw == (raw_classes != nullptr), "%s: the raw peaks are all three or none", who);
+  if (const int e = topk_check_geometry(who, B, C, H, W, K)) return e;
+  if (table_ab || table_b) {
+    CF_REQUIRE((long)B * H * W < (1L << 31), "%s: B * HW must stay below 2^31 (flat pixels are int32)", who);
+    CF_REQUIRE((long)B * (2L * K + CF_HEAD_AT_SLOTS) < (1L << 31), "%s: B * K too large", who);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t set_stride = (size_t)B * TOPK_SLICES * K;
+  uint64_t* keys = static_cast<uint64_t*>(workspace);
+  if (topk_fused_reg(C, H, W)) {
+    const auto kernel = raw ? topk_slice_reg_nms_kernel<true> : topk_slice_reg_nms_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(B * TOPK_SLICES), dim3(TOPK_RT), 0, st, heat, C, H, W, K, keys, set_stride);
+  } else {
+    if (raw)
+      if (const int e = topk_launch_slices(who, heat, B, C, H, W, K, 0, keys, st)) return e;
+    if (const int e = topk_launch_slices(who, heat, B, C, H, W, K, 2, keys + set_stride, st)) return e;
+  }
+  static CfLdsLimit merge_limit;
+  merge_limit.ensure(topk_merge_fused_kernel, topk_merge_lds_bytes(K), 65536);
+  hipLaunchKernelGGL(topk_merge_fused_kernel, dim3(B * (raw ? 2 : 1)), dim3(TOPK_MERGE_THREADS), topk_merge_lds_bytes(K), st,
+                     static_cast<const uint64_t*>(keys), set_stride, B, K, H * W, TopkPeakOut{raw_scores, raw_inds, raw_classes},
+                     TopkPeakOut{scores, inds, classes}, table_ab, table_b);
+  return cf_check_launch(who);
 }
 
 namespace {

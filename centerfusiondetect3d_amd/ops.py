@@ -1069,6 +1069,28 @@ def topk_peaks(heat, K=100, nms=False, out=None, only_if_changed=None):
     return scores, inds, classes
 
 
+def topk_peaks_fused(heat, K=100, want_raw=True, want_tables=True):
+    """cf_topk_peaks_fused: the NMS'd peaks (= topk_peaks(heat, K, nms=2)) [and the raw ones (= topk_peaks(heat, K))] from one
+    read of the (B,C,H,W) map, and the slot tables of cf_head_fused_at built from them (= cf_head_slot_tables) - two launches.
+    -> (raw | None, nms, table_ab | None, table_b | None); raw / nms = (scores (B,K) f32, inds (B,K) i32, classes (B,K) i32),
+    table_ab (B, ceil(2K / 18), 18) i32, table_b (B, ceil(K / 18), 18) i32."""
+    _need_cuda(heat)
+    if not heat.is_contiguous():
+        heat = heat.contiguous()
+    B, Cc, H, W = heat.shape
+    dev = heat.device
+    new = lambda: (torch.empty((B, K), device=dev, dtype=torch.float32), torch.empty((B, K), device=dev, dtype=torch.int32),
+                   torch.empty((B, K), device=dev, dtype=torch.int32))
+    raw, nms = (new() if want_raw else (None, None, None)), new()
+    t_ab = torch.empty((B, -(-2 * K // 18), 18), device=dev, dtype=torch.int32) if want_tables else None
+    t_b = torch.empty((B, -(-K // 18), 18), device=dev, dtype=torch.int32) if want_tables else None
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.cf_topk_peaks_fused_workspace_bytes(B, Cc, H, W, K)), device=dev, dtype=torch.uint8)
+    _lib.check(lib.cf_topk_peaks_fused(heat.data_ptr(), B, Cc, H, W, K, *(_lib.ptr(t) for t in raw), *(t.data_ptr() for t in nms),
+                                       _lib.ptr(t_ab), _lib.ptr(t_b), ws.data_ptr(), _lib.stream_ptr()), "cf_topk_peaks_fused")
+    return (raw if want_raw else None), nms, t_ab, t_b
+
+
 def frustum_assoc(inds, depth, wh, dim, rot, calib, pc_dep, max_pc_dist=60.0, want_nhwc4=False,
                   pc_hm=None, pc_hm_nhwc4=None, pc_hm_split8=None):
     _need_cuda(inds, depth, wh, dim, rot, calib, pc_dep)

@@ -431,7 +431,9 @@ class _Plan:
         tiles_b, tiles_ab = -(-K // AT_SLOTS), -(-2 * K // AT_SLOTS)
         self.at = dict(f_hm=f_hm, flops_hm=B * self.h4 * self.w4 * px_hm, f_rest=f_rest, px_rest=px_rest,
                        tab_b=self._buf(B * tiles_b * AT_SLOTS, dtype=torch.int32), n_b=B * tiles_b,
-                       tab_ab=self._buf(B * tiles_ab * AT_SLOTS, dtype=torch.int32) if self.frustum else None, n_ab=B * tiles_ab)
+                       tab_ab=self._buf(B * tiles_ab * AT_SLOTS, dtype=torch.int32) if self.frustum else None, n_ab=B * tiles_ab,
+                       ws=self._buf(max(1, self.lib.cf_topk_peaks_fused_workspace_bytes(B, self._m.config.heads["heatmap"], self.h4,
+                                                                                        self.w4, K)), dtype=torch.uint8))
 
     def _peaks_lane(self):
         """the side lane: starts behind whatever the caller's stream has issued so far, runs the decoder's NMS + top-k"""
@@ -717,8 +719,10 @@ class _Plan:
         if at is None:
             self._launch(st)
         else:
-            topk = (lib.cf_topk_peaks, hm.data_ptr(), B, heads["heatmap"], h4, w4, K, 0, *tk) if self.frustum else None
-            self._launch(st, self._at_seq(at, peaks, topk, pk_i))
+            raw = tk[:3] if self.frustum else (None, None, None)   # (the frustum chain's top-K: from the same read of the map)
+            fused = (hm.data_ptr(), B, heads["heatmap"], h4, w4, K, *raw, pk_s.data_ptr(), pk_i.data_ptr(), pk_c.data_ptr(),
+                     at["tab_ab"].data_ptr() if self.frustum else None, at["tab_b"].data_ptr(), at["ws"].data_ptr())
+            self._launch(st, self._at_seq(at, (_peaks_fused_and_checksum, lib, fused, peaks[3])))
             y = self._pending(y, model, written)
         if self.peaks_step is not None and peaks_on:
             # (decode.py re-checks the map's contents against pk_sum[0] on the device before it trusts the peaks)
@@ -729,21 +733,21 @@ class _Plan:
         return [y]
 
     # ------------------------------------------------------------------------------------------ heads at the peaks
-    def _at_seq(self, at, peaks, topk, pk_i):
+    def _at_seq(self, at, peaks):
         """The launch list of an at-peaks forward: the plan's steps with the head groups replaced.  `tails.primary` = the dense
-        heat-map head (cf_head_fused on that head alone), followed IN LINE by the frustum chain's top-K (`topk`, frustum models),
-        the decoder's NMS + top-K + checksum (`peaks`; its lane stays empty), the slot tables and the other primary heads at the
-        listed pixels; `tails.chained` / `tails.secondary` = those groups at the decoder's peaks (cf_head_fused_at).  The step
-        FLOPs under the three names are set to what these launches compute.  (The decoder's pass on the side lane beside the
-        chain's top-K, joined in front of the tables, measured no faster: docs/experiments/heads_at_peaks.md.)"""
+        heat-map head (cf_head_fused on that head alone), followed IN LINE by the index pass (`peaks`: cf_topk_peaks_fused - the
+        frustum chain's top-K on frustum models, the decoder's NMS + top-K and the slot tables, two launches - and the checksum;
+        the decoder's lane stays empty) and the other primary heads at the listed pixels; `tails.chained` / `tails.secondary` =
+        those groups at the decoder's peaks (cf_head_fused_at).  `at.topk` and `at.tables`, launches of their own before the
+        fused pass, issue nothing.  The step FLOPs under the three names are set to what these launches compute.  (The
+        decoder's pass on the side lane beside the chain's top-K, joined in front of the tables, measured no faster:
+        docs/experiments/heads_at_peaks.md.)"""
         lib, idx = self.lib, self.step_index
         tab_b, n_b = at["tab_b"].data_ptr(), at["n_b"]
         tab_p, n_p = (at["tab_ab"].data_ptr(), at["n_ab"]) if self.frustum else (tab_b, n_b)
-        HP_PX = 128                                        # pixel columns a virtual tile computes (18 of them are written)
-        extra = ([("at.topk", topk, 0)] if topk is not None else []) + [("at.peaks", peaks, 0)]
-        extra += [
-                  ("at.tables", (lib.cf_head_slot_tables, self.tk_inds.data_ptr() if self.frustum else None, pk_i.data_ptr(),
-                                 self.B, self.K, self.h4 * self.w4, at["tab_ab"].data_ptr() if self.frustum else None, tab_b), 0),
+        HP_PX = 48                                         # pixel columns a virtual tile computes: its three centre rows (18 of them are written)
+        extra = ([("at.topk", (_no_launch,), 0)] if self.frustum else []) + [
+                  ("at.peaks", peaks, 0), ("at.tables", (_no_launch,), 0),
                   ("at.primary", (lib.cf_head_fused_at, C.byref(at["f_rest"]), tab_p, n_p), 0)]
         repl = {idx["tails.primary"]: (lib.cf_head_fused, C.byref(at["f_hm"]))}
         self.step_flops["tails.primary"] = at["flops_hm"]
@@ -828,6 +832,12 @@ def _early_input(x, pc, x8, stream):
 def _no_launch(stream):
     """a plan step that issues nothing (status 0)"""
     return 0
+
+
+def _peaks_fused_and_checksum(lib, fused_args, sum_args, stream):
+    """the index pass of an at-peaks forward (both top-K lists and the slot tables) and the checksum of the map (one plan step)"""
+    rc = lib.cf_topk_peaks_fused(*fused_args, stream)
+    return rc if rc != 0 else lib.cf_checksum64(*sum_args, stream)
 
 
 def _peaks_and_checksum(lib, topk_args, sum_args, stream):

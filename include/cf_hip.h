@@ -317,6 +317,7 @@ int cf_head_fused_with(const cf_head_fused_args* a, int tile, int pc_skip, void*
  * list_b (entries K..2K-1), table_b [B][ceil(K / 18)][18] from list_b alone.  Either table may be NULL.  Every entry in
  * [0, HW) gets a slot, entries outside get -1, the padding up to a whole tile is -1.  No reference counterpart: the
  * reference evaluates every head at every pixel (model/networks/detectHeads.py:117-191) and reads them at the peaks. */
+#define CF_HEAD_AT_SLOTS 18                /* listed pixels per virtual tile */
 int cf_head_fused_at(const cf_head_fused_args* a, const int32_t* slot_pixels, int n_tiles, void* stream);
 int cf_head_slot_tables(const int32_t* list_a, const int32_t* list_b, int B, int K, int HW, int32_t* table_ab,
                         int32_t* table_b, void* stream);
@@ -514,6 +515,19 @@ int cf_topk_peaks_if_changed(const float* heat, int B, int C, int H, int W, int 
                              int32_t* classes, void* workspace, const unsigned long long* sums, void* stream);
 int cf_topk_peaks(const float* heat, int B, int C, int H, int W, int K, int nms, float* scores,
                   int32_t* inds, int32_t* classes, void* workspace, void* stream);
+/* (added under ABI 7) cf_topk_peaks_fused: the index pass of a forward whose heads run at the peaks, in TWO launches: the
+ * NMS'd peaks of cf_topk_peaks(heat, nms = 2) in scores / inds / classes and - optional, all three or none - the raw peaks of
+ * cf_topk_peaks(heat, nms = 0) in raw_scores / raw_inds / raw_classes, both from one read of the map (the 3x3 equality NMS is
+ * applied inside the slice kernel: no suppressed map), one merge launch for both - which also writes, if not NULL, the
+ * tables cf_head_slot_tables(raw_inds, inds, B, K, H * W, table_ab, table_b) would write (same shapes, same entries; without
+ * the raw peaks table_ab holds -1 where they would stand).  Bit for bit the results of those calls.  Maps whose slices do not
+ * fit the register-cached kernel (more than 16 x 16,384 elements per image) take cf_topk_peaks' own slice passes in front of
+ * the one merge.  workspace: cf_topk_peaks_fused_workspace_bytes(B, C, H, W, K) bytes.  Meant for a stream with nothing
+ * beside it: its 1024-thread workgroups do not fit next to a head launch's. */
+size_t cf_topk_peaks_fused_workspace_bytes(int B, int C, int H, int W, int K);
+int cf_topk_peaks_fused(const float* heat, int B, int C, int H, int W, int K, float* raw_scores, int32_t* raw_inds,
+                        int32_t* raw_classes, float* scores, int32_t* inds, int32_t* classes, int32_t* table_ab,
+                        int32_t* table_b, void* workspace, void* stream);
 
 /* cf_frustum_assoc: radar frustum association for K peaks per image.
  * replaces utils/pointcloud.py:331-394 (getPcFrustumHeatmap, after its topk) and 397-481
