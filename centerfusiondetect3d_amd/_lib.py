@@ -167,6 +167,7 @@ SYMBOLS = {
     "cf_conv3x3_proj_f16x3": (_i, [C.POINTER(ConvArgs), C.POINTER(C.c_int32), _f]),
     "cf_conv3x3_f16x3_grouped": (_i, [C.POINTER(C.POINTER(ConvArgs)), C.c_int32, _f]),
     "cf_conv3x3_grouped_form": (_i, [C.POINTER(C.POINTER(ConvArgs)), C.c_int32, C.POINTER(C.c_int32)]),
+    "cf_conv3x3_tile_form": (_i, [C.c_int32, C.POINTER(C.POINTER(ConvArgs)), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cf_stem_fused": (_i, [C.POINTER(StemArgs), _f]),
     "cf_stem_fused_early": (_i, [C.POINTER(StemEarlyArgs), _f]),
     "cf_split_bf16": (_i, [_f, _f, C.c_long, _i, _i, _i, _f]),
@@ -181,6 +182,7 @@ SYMBOLS = {
     "cf_dcn_v2_f16x3": (_i, [C.POINTER(DcnArgs), _f]),
     "cf_dcn_v2_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
     "cf_dcn_v2_f16x3_grouped": (_i, [C.POINTER(C.POINTER(DcnArgs)), C.c_int32, _f]),
+    "cf_dcn_v2_f16x3_form": (_i, [C.POINTER(C.POINTER(DcnArgs)), C.c_int32, C.POINTER(C.c_int32)]),
     "cf_gemm_tile_form": (_i, [C.c_long, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cf_dcn_v2_bwd_data": (_i, [C.POINTER(DcnBwdArgs), _f]),
     "cf_dcn_v2_bwd_weight": (_i, [C.POINTER(DcnBwdArgs), _f]),

@@ -335,11 +335,64 @@ int dcn_k_split(int H, int W, int n_chunks, int n_pad) {
   return ks;
 }
 
-template <typename K, typename A>
-void launch_f16(K kernel, dim3 grid, size_t dyn, hipStream_t st, const A& args) {
+template <typename K, typename... A>
+void launch_f16(K kernel, dim3 grid, size_t dyn, hipStream_t st, const A&... args) {
   static CfLdsLimit lds_limit;  // one per template instantiation
   lds_limit.ensure(kernel, dyn, 16384);
-  hipLaunchKernelGGL(kernel, grid, dim3(256), dyn, st, args);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), dyn, st, args...);
+}
+
+// The tile form of a DCN launch: dcn_f16x3_kernel<WC, WP, RT, COAL, CT> (n_groups > 1: dcn_f16x3_kernel_grouped) on the grid
+// (n_groups x tiles, grid_y, ks).
+struct DcnForm {
+  int WC, WP, RT;
+  bool COAL;
+  int CT;
+  unsigned tiles, grid_y, ks;
+};
+
+// The one place that form is chosen (cf_dcn_v2_f16x3_form reports it, cf_dcn_v2_f16x3 and _grouped run it): M pixels per
+// group, ks from dcn_k_split, G groups - the small-grid rule sees the whole grid, it changes no sum.
+DcnForm dcn_pick(long M, int N, int N_pad, unsigned ks, long G) {
+  const bool coal = (N & 3) == 0;   // whole-row epilogue through LDS
+  const unsigned tiles64 = (unsigned)((M + 63) / 64), tiles128 = (unsigned)((M + 127) / 128);
+  // SMALL GRIDS (small batches): 64 output channels on 64-pixel tiles (the 128-channel configuration with two of its
+  // four channel-group waves idle in the MFMAs, all four staging) while that launch still fits the chip in one round:
+  // 128 -> 64 at 56x100, bs=1: 30.4 vs 43.4 us, bs=2: 31.6 vs 45.0 us; at 350 workgroups the gain is gone.  Same K order,
+  // same K split: bit-identical, so the choice may depend on the batch size (as in cf_conv3x3_f16x3).
+  if (N_pad <= 64 && (M + 63) / 64 * (long)ks * G <= 256) return {4, 1, 1, coal, 2, tiles64, 1u, ks};
+  // 64 channels: 2 x 32-channel wave rows, 2 x 64 pixels - or, with the whole-row epilogue,
+  // half-size pixel tiles (32 pixels per wave: 114 registers, 39 KB of LDS - four workgroups per CU instead of two): the parts
+  // of this kernel add up instead of overlapping (docs/experiments/r5_dcn_attribution.md), so a third wave per SIMD pays
+  // wherever the grid is not many rounds deep - 8 x 64 -> 64 at 112 x 200: 116.5 vs 123.5 us, 8 x 128 -> 64 at 56 x 100: 61.1 vs
+  // 72.6 us, 16 x 64 -> 64 at 112 x 200: equal; step 7.75 vs 7.80 ms.  Same K order: bit-identical.
+  if (N_pad <= 64) return {2, 2, 1, coal, coal ? 1 : 2, coal ? tiles64 : tiles128, (unsigned)((N_pad + 63) / 64), ks};
+  // 128 channels: 4 x 32-channel wave rows, 64 pixels
+  if (N_pad <= 128) return {4, 1, 1, coal, 2, tiles64, (unsigned)((N_pad + 127) / 128), ks};
+  return {4, 1, 2, coal, 2, tiles64, (unsigned)((N_pad + 255) / 256), ks};
+}
+
+// The instantiated forms: X(WC, WP, RT, COAL, CT, has a grouped instantiation)
+#define CF_DCN_TILES(X)      \
+  X(4, 1, 1, true, 2, true)  \
+  X(4, 1, 1, false, 2, false) \
+  X(2, 2, 1, true, 1, true)  \
+  X(2, 2, 1, false, 2, false) \
+  X(4, 1, 2, true, 2, false) \
+  X(4, 1, 2, false, 2, false)
+
+// launches f if it is this instantiation: on grid (tiles, grid_y, ks), or (g != nullptr) the grouped form on (n_groups x tiles, grid_y, ks)
+template <int WC, int WP, int RT, bool COAL, int CT, bool HAS_GRP>
+bool dcn_launch_if(const DcnForm& f, const DcnF& k, DcnG* g, int n_groups, hipStream_t st) {
+  if (f.WC != WC || f.WP != WP || f.RT != RT || f.COAL != COAL || f.CT != CT || (g && !HAS_GRP)) return false;
+  if (!g) launch_f16(dcn_f16x3_kernel<WC, WP, RT, COAL, CT>, dim3(f.tiles, f.grid_y, f.ks), 0, st, k);
+  if constexpr (HAS_GRP) {
+    if (g) {
+      g->n_tiles = (int)f.tiles;
+      launch_f16(dcn_f16x3_kernel_grouped<WC, WP, RT, COAL, CT>, dim3(f.tiles * (unsigned)n_groups, f.grid_y, f.ks), 0, st, k, *g);
+    }
+  }
+  return true;
 }
 
 }  // namespace
@@ -396,7 +449,8 @@ extern "C" int cf_conv2d_f16x3(const cf_conv_args* a, void* stream) {
 // gs == nullptr: the launch of cf_dcn_v2_f16x3.  Otherwise a == gs[0] and the n_groups (>= 2) validated blocks of
 // cf_dcn_v2_f16x3_grouped: the same code picks the K split and the tile form (the small-grid rule sees the whole grid - it
 // changes no sum), the grid is n_groups times as wide in x, and ONE reduction runs over every group's rows.
-static int dcn_f16x3_impl(const cf_dcn_args* a, const cf_dcn_args* const* gs, int n_groups, void* stream) {
+// report != nullptr (cf_dcn_v2_f16x3_form): validate and pick as the launch does, write the answer, touch no runtime.
+static int dcn_f16x3_impl(const cf_dcn_args* a, const cf_dcn_args* const* gs, int n_groups, void* stream, int32_t* report = nullptr) {
   CF_REQUIRE(a != nullptr, "cf_dcn_v2_f16x3: null args");
   CF_REQUIRE(a->C > 0 && a->C % 32 == 0, "cf_dcn_v2_f16x3: C=%d not a multiple of 32", a->C);
   CF_REQUIRE(a->N > 0 && a->N_pad >= a->N && a->N_pad % 32 == 0, "cf_dcn_v2_f16x3: N=%d N_pad=%d", a->N, a->N_pad);
@@ -449,44 +503,19 @@ static int dcn_f16x3_impl(const cf_dcn_args* a, const cf_dcn_args* const* gs, in
     g.out_scale[i] = rg.out_scale[i] = gs[i]->out_scale;
     CF_REQUIRE(g.in_scale[i] > 0.0f, "cf_dcn_v2_f16x3_grouped: in_scale must be 0 (= 16) or a power of two");
   }
-  // one launch of `kernel` on grid (tiles, y, ks), or of its grouped form on (n_groups x tiles, y, ks)
-  auto launch = [&](auto kernel, auto kernel_g, dim3 grid) {
-    if (!gs) return launch_f16(kernel, grid, 0, st, k);
-    g.n_tiles = (int)grid.x;
-    grid.x *= (unsigned)n_groups;
-    static CfLdsLimit lds_limit;
-    lds_limit.ensure(kernel_g, 0, 16384);
-    hipLaunchKernelGGL(kernel_g, grid, dim3(256), 0, st, k, g);
-  };
   k.mask_activated = a->mask_activated;
-  const bool coal = (a->N & 3) == 0;   // whole-row epilogue through LDS
-  CF_REQUIRE(!a->out_mx || coal, "cf_dcn_v2_f16x3: the mx output is written by the whole-row epilogue (N %% 4 == 0)");
-  // SMALL GRIDS (small batches): 64 output channels on 64-pixel tiles (the 128-channel configuration with two of its
-  // four channel-group waves idle in the MFMAs, all four staging) while that launch still fits the chip in one round:
-  // 128 -> 64 at 56x100, bs=1: 30.4 vs 43.4 us, bs=2: 31.6 vs 45.0 us; at 350 workgroups the gain is gone.  Same K order,
-  // same K split: bit-identical, so the choice may depend on the batch size (as in cf_conv3x3_f16x3).
-  if (a->N_pad <= 64 && (M + 63) / 64 * (long)ks * G <= 256) {
-    const dim3 grid((unsigned)((M + 63) / 64), 1u, ks);
-    if (coal) launch(dcn_f16x3_kernel<4, 1, 1, true>, dcn_f16x3_kernel_grouped<4, 1, 1, true>, grid);
-    else launch_f16(dcn_f16x3_kernel<4, 1, 1, false>, grid, 0, st, k);
-  } else if (a->N_pad <= 64) {          // 64 channels: 2 x 32-channel wave rows, 2 x 64 pixels
-    // half-size pixel tiles (32 pixels per wave: 114 registers, 39 KB of LDS - four workgroups per CU instead of two): the parts
-    // of this kernel add up instead of overlapping (docs/experiments/r5_dcn_attribution.md), so a third wave per SIMD pays
-    // wherever the grid is not many rounds deep - 8 x 64 -> 64 at 112 x 200: 116.5 vs 123.5 us, 8 x 128 -> 64 at 56 x 100: 61.1 vs
-    // 72.6 us, 16 x 64 -> 64 at 112 x 200: equal; step 7.75 vs 7.80 ms.  Same K order: bit-identical.
-    const dim3 grid((unsigned)((M + 127) / 128), (unsigned)((a->N_pad + 63) / 64), ks);
-    const dim3 grid1((unsigned)((M + 63) / 64), (unsigned)((a->N_pad + 63) / 64), ks);
-    if (coal) launch(dcn_f16x3_kernel<2, 2, 1, true, 1>, dcn_f16x3_kernel_grouped<2, 2, 1, true, 1>, grid1);
-    else launch_f16(dcn_f16x3_kernel<2, 2, 1, false>, grid, 0, st, k);
-  } else if (a->N_pad <= 128) {  // 128 channels: 4 x 32-channel wave rows, 64 pixels
-    const dim3 grid((unsigned)((M + 63) / 64), (unsigned)((a->N_pad + 127) / 128), ks);
-    if (coal) launch(dcn_f16x3_kernel<4, 1, 1, true>, dcn_f16x3_kernel_grouped<4, 1, 1, true>, grid);
-    else launch_f16(dcn_f16x3_kernel<4, 1, 1, false>, grid, 0, st, k);
-  } else {
-    const dim3 grid((unsigned)((M + 63) / 64), (unsigned)((a->N_pad + 255) / 256), ks);
-    if (coal) launch_f16(dcn_f16x3_kernel<4, 1, 2, true>, grid, 0, st, k);
-    else launch_f16(dcn_f16x3_kernel<4, 1, 2, false>, grid, 0, st, k);
+  CF_REQUIRE(!a->out_mx || (a->N & 3) == 0, "cf_dcn_v2_f16x3: the mx output is written by the whole-row epilogue (N %% 4 == 0)");
+  const DcnForm f = dcn_pick(M, a->N, a->N_pad, ks, G);
+  if (report) {
+    const int32_t v[9] = {f.WC, f.WP, f.RT, f.COAL, f.CT, (int32_t)(f.tiles * G), (int32_t)f.grid_y, (int32_t)f.ks, (int32_t)f.tiles};
+    for (int i = 0; i < 9; ++i) report[i] = v[i];
+    return CF_OK;
   }
+  bool launched = false;
+#define X(WC, WP, RT, COAL, CT, HAS_GRP) launched = launched || dcn_launch_if<WC, WP, RT, COAL, CT, HAS_GRP>(f, k, gs ? &g : nullptr, n_groups, st);
+  CF_DCN_TILES(X)
+#undef X
+  CF_REQUIRE(launched, "cf_dcn_v2_f16x3: the picked form <%d, %d, %d, %d, %d>%s is not instantiated", f.WC, f.WP, f.RT, f.COAL, f.CT, gs ? " (grouped)" : "");
   if (ks > 1) {
     const int ns4 = k.n_rt * 32 / 4;
     const long MN4 = G * M * ns4;
@@ -504,10 +533,10 @@ static int dcn_f16x3_impl(const cf_dcn_args* a, const cf_dcn_args* const* gs, in
 
 extern "C" int cf_dcn_v2_f16x3(const cf_dcn_args* a, void* stream) { return dcn_f16x3_impl(a, nullptr, 1, stream); }
 
-extern "C" int cf_dcn_v2_f16x3_grouped(const cf_dcn_args* const* gs, int32_t n_groups, void* stream) {
+static int dcn_f16x3_grouped_impl(const cf_dcn_args* const* gs, int32_t n_groups, void* stream, int32_t* report) {
   CF_REQUIRE(gs != nullptr && n_groups >= 1 && n_groups <= CF_MAX_GROUPS, "cf_dcn_v2_f16x3_grouped: n_groups=%d outside 1..%d", n_groups, CF_MAX_GROUPS);
   for (int g = 0; g < n_groups; ++g) CF_REQUIRE(gs[g] != nullptr, "cf_dcn_v2_f16x3_grouped: group %d is null", g);
-  if (n_groups == 1) return cf_dcn_v2_f16x3(gs[0], stream);
+  if (n_groups == 1) return dcn_f16x3_impl(gs[0], nullptr, 1, stream, report);
   const cf_dcn_args* a = gs[0];
   CF_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0 && a->om_stride > 0 && a->out_stride > 0 && a->N > 0, "cf_dcn_v2_f16x3_grouped: bad geometry");
   const size_t M = (size_t)a->B * a->H * a->W;
@@ -524,7 +553,16 @@ extern "C" int cf_dcn_v2_f16x3_grouped(const cf_dcn_args* const* gs, int32_t n_g
     CF_REQUIRE(b->offmask == a->offmask + g * M * a->om_stride && b->out == a->out + g * M * a->out_stride,
                "cf_dcn_v2_f16x3_grouped: group %d must use rows [g M, (g + 1) M) of group 0's offmask / out buffers", g);
   }
-  return dcn_f16x3_impl(a, gs, n_groups, stream);
+  return dcn_f16x3_impl(a, gs, n_groups, stream, report);
+}
+
+extern "C" int cf_dcn_v2_f16x3_grouped(const cf_dcn_args* const* gs, int32_t n_groups, void* stream) {
+  return dcn_f16x3_grouped_impl(gs, n_groups, stream, nullptr);
+}
+
+extern "C" int cf_dcn_v2_f16x3_form(const cf_dcn_args* const* gs, int32_t n_groups, int32_t* form) {
+  CF_REQUIRE(form != nullptr, "cf_dcn_v2_f16x3_form: null output");
+  return dcn_f16x3_grouped_impl(gs, n_groups, nullptr, form);
 }
 
 extern "C" size_t cf_dcn_v2_workspace_bytes(int B, int H, int W, int C, int N_pad) {

@@ -173,6 +173,31 @@ def conv3x3_grouped_form(blocks):
     return dict(zip(("WC", "WP", "WK", "NU", "T2", "CT"), form))
 
 
+CONV3_ENTRIES = {"plain": 0, "root": 1, "proj": 2, "grouped": 3}            # CF_CONV3_ENTRY_*
+CONV3_FORM_FIELDS = ("patch", "fused", "WC", "WP", "WK", "RT", "NU", "DB", "MINB", "T2", "CT", "S2", "ROOT", "PROJ", "GRP",
+                     "blocks", "grid_y", "threads", "lds", "PR", "tiles_x", "tiles_y", "n_rounds")
+DCN_FORM_FIELDS = ("WC", "WP", "RT", "COAL", "CT", "grid_x", "grid_y", "ks", "tiles")
+
+
+def conv3x3_tile_form(entry, blocks, channels=None):
+    """What cf_conv3x3_f16x3 ("plain": one block), cf_conv3x3_root_f16x3 ("root": conv2's block, the Root's, root channels),
+    cf_conv3x3_proj_f16x3 ("proj": one block, source channels) or cf_conv3x3_f16x3_grouped ("grouped") would launch for
+    these argument blocks, as CONV3_FORM_FIELDS (cf_conv3x3_tile_form: the launchers' own choice; host only, nothing is
+    launched).  patch = 0: forwarded to cf_conv2d_f16x3, every form field -1."""
+    form = (C.c_int32 * len(CONV3_FORM_FIELDS))()
+    ch = None if channels is None else (C.c_int32 * len(channels))(*channels)
+    _lib.check(_lib.load().cf_conv3x3_tile_form(CONV3_ENTRIES[entry], group_ptrs(blocks), len(blocks), ch, form), "cf_conv3x3_tile_form")
+    return dict(zip(CONV3_FORM_FIELDS, form))
+
+
+def dcn_v2_f16x3_form(blocks):
+    """What cf_dcn_v2_f16x3_grouped (one block: cf_dcn_v2_f16x3) would launch for these argument blocks, as DCN_FORM_FIELDS
+    (cf_dcn_v2_f16x3_form: the launchers' own choice; host only, nothing is launched)."""
+    form = (C.c_int32 * len(DCN_FORM_FIELDS))()
+    _lib.check(_lib.load().cf_dcn_v2_f16x3_form(group_ptrs(blocks), len(blocks), form), "cf_dcn_v2_f16x3_form")
+    return dict(zip(DCN_FORM_FIELDS, form))
+
+
 def dcn_v2_f16x3_grouped(pds: Sequence[PackedDcn], xs, offmask, act=ACT_RELU, k_split=True, in_scales=None):
     """The deformable convolutions of up to four same-shape layers as ONE launch (+ one reduction on K-split maps;
     cf_dcn_v2_f16x3_grouped).  xs: (B,H,W,C) tensors (two groups may share one); offmask (G,B,H,W,S>=27); -> (G,B,H,W,N).

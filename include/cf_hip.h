@@ -182,6 +182,27 @@ int cf_conv3x3_f16x3_grouped(const cf_conv_args* const* groups, int32_t n_groups
  * wave} (the template arguments of conv3x3_f16x3_kernel_grouped): host arithmetic only, chosen by the launcher's own code. */
 int cf_conv3x3_grouped_form(const cf_conv_args* const* groups, int32_t n_groups, int32_t* form);
 
+/* cf_conv3x3_tile_form (added within ABI 7: nothing existing changed): what a call of one of the four cf_conv3x3_* entry points
+ * would launch, from the argument blocks that call takes - the launchers' own rule (cf_conv3x3_f16.hip: conv3_pick), host
+ * arithmetic only: no stream, nothing launched, the HIP runtime is not touched.  `entry` names the entry point:
+ *   CF_CONV3_ENTRY_PLAIN    blocks[0] = the block of cf_conv3x3_f16x3 (stride 1 or 2), n_blocks = 1, channels = NULL
+ *   CF_CONV3_ENTRY_ROOT     blocks[0] = conv, blocks[1] = root, n_blocks = 2, channels = root_channels
+ *   CF_CONV3_ENTRY_PROJ     blocks[0] = the block of cf_conv3x3_proj_f16x3, n_blocks = 1, channels = src_channels
+ *   CF_CONV3_ENTRY_GROUPED  blocks = groups, n_blocks = n_groups, channels = NULL (one group: the answer for cf_conv3x3_f16x3)
+ * The blocks are validated as the launch validates them: what it refuses returns CF_EINVAL here.  form[CF_CONV3_FORM_INTS]:
+ *   [0]  1: the LDS-patch kernel runs; 0: the call is forwarded to cf_conv2d_f16x3 (a stride-2 block with a residual is
+ *        forwarded before the rest of its validation, which is then that entry point's) - entries 2.. are -1
+ *   [1]  ROOT entry: 1 = conv2 and the Root run as ONE launch; 0 = two launches, and the answer describes conv2's
+ *   [2..14]  the kernel's template arguments WC, WP, WK, RT, NU, DB, MINB, T2, CT, S2, ROOT, PROJ, GRP
+ *   [15..22] workgroups in x (per group: a grouped launch has n_groups times as many), gridDim.y, threads, dynamic LDS bytes,
+ *        patch rows PR, tiles_x, tiles_y (tiled patches, else 0), rounds of the slice loop */
+#define CF_CONV3_ENTRY_PLAIN 0
+#define CF_CONV3_ENTRY_ROOT 1
+#define CF_CONV3_ENTRY_PROJ 2
+#define CF_CONV3_ENTRY_GROUPED 3
+#define CF_CONV3_FORM_INTS 23
+int cf_conv3x3_tile_form(int32_t entry, const cf_conv_args* const* blocks, int32_t n_blocks, const int32_t* channels, int32_t* form);
+
 /* ---- (ABI 5) host-side weight preparation: SURVEY 8(b) "cf_pack_weights" (one-time BN fold + layout) -------------------------
  * Pure CPU functions (no stream, no device memory): HOST pointers in, HOST buffers out; the caller copies the results to the
  * device once.  They do what centerfusiondetect3d_amd/packing.py does for the Python host - the same arithmetic operation for
@@ -386,6 +407,13 @@ size_t cf_dcn_v2_workspace_bytes(int B, int H, int W, int C, int N_pad);
  * split).  out_split_bf16 / out_mx are refused (CF_EINVAL) when n_groups > 1.  Group g's rows equal cf_dcn_v2_f16x3 on block g
  * (same workspace choice) bit for bit: same descriptors, same K order, same K split, partial sums added in the same order. */
 int cf_dcn_v2_f16x3_grouped(const cf_dcn_args* const* groups, int32_t n_groups, void* stream);
+/* ... and what that call (one group: cf_dcn_v2_f16x3 on groups[0]) would launch, by the launchers' own rule (cf_gemm_f16.hip:
+ * dcn_pick; K split: dcn_k_split, taken only when the block carries a workspace) - validated as the launch, host arithmetic
+ * only, the HIP runtime is not touched (added within ABI 7).  form[CF_DCN_FORM_INTS] = {WC, WP, RT, COAL, CT: the template
+ * arguments of dcn_f16x3_kernel (two or more groups: dcn_f16x3_kernel_grouped); gridDim.x, gridDim.y, K parts (gridDim.z;
+ * above 1 a reduction launch follows); workgroups in x per group} */
+#define CF_DCN_FORM_INTS 9
+int cf_dcn_v2_f16x3_form(const cf_dcn_args* const* groups, int32_t n_groups, int32_t* form);
 
 /* What cf_conv2d_fused (dcn = 0) / cf_dcn_v2_fused (dcn = 1) launches for M output pixels: *kind 0 = the 32x32x2 tile
  * kernel, 1 = the 16-channel kernel; *bm x *bn its tile.  Host arithmetic only, nothing is launched.  The launchers

@@ -190,9 +190,9 @@ CONV_CASES = {
     "patch_64x64_res": _conv("patch", 1, 64, 64, 28, 50, 1, 1, True, "patch:residual"),
     "patch_256_wave_pairs": _conv("patch", 2, 256, 256, 14, 25, 1, 1, True, "patch:wave_pairs"),
     "patch_512": _conv("patch", 1, 512, 512, 7, 13, 1, 1, False, "patch:512_channels"),
-    "patch_5x300_forwarded": _conv("patch", 1, 64, 64, 5, 300, 1, 1, False, "patch:forwarded_to_slot"),
+    "patch_5x300_forwarded": _conv("patch", 14, 64, 64, 5, 300, 1, 1, False, "patch:forwarded_to_slot"),
     "patch_127x127_2d": _conv("patch", 2, 32, 27, 127, 127, 1, 0, False, "patch:2d"),
-    "patch_37x150_tiled": _conv("patch", 2, 128, 128, 37, 150, 1, 1, False, "patch:tiled"),
+    "patch_37x150_tiled": _conv("patch", 3, 128, 128, 37, 150, 1, 1, False, "patch:tiled"),
     "s2_32x64_45x67": _conv("patch", 1, 32, 64, 45, 67, 2, 1, False, "patch_s2:odd_sizes"),
     "s2_64x128_17x31": _conv("patch", 3, 64, 128, 17, 31, 2, 1, False, "patch_s2:ragged"),
     "s2_16x64_8x6": _conv("patch", 2, 16, 64, 8, 6, 2, 1, False, "patch_s2:one_slice"),
@@ -232,6 +232,36 @@ DCN_CASES = {
     "dcn_64_64_37x70": (1, 64, 64, 37, 70, 0.5, "dcn:ragged_64"),
     "dcn_32_48": (1, 32, 48, 50, 45, 1.0, "dcn:48_of_64_rows"),
 }
+
+
+def _tile(WC, WP, WK, RT, NU, T2, CT, **more):
+    return dict(patch=1, WC=WC, WP=WP, WK=WK, RT=RT, NU=NU, T2=T2, CT=CT, **more)
+
+
+# The tiling every row above is there for, as the launchers report it (cf_conv3x3_tile_form: ops.CONV3_FORM_FIELDS;
+# cf_dcn_v2_f16x3_form: ops.DCN_FORM_FIELDS) - tests/test_f16x3_forms_cpu.py asserts it, so a moved threshold cannot move a case onto
+# another kernel unseen.  patch = 0: forwarded to the slot kernel; fused: conv2 + Root as one launch.
+CONV_TILINGS = {
+    "patch_64x27_wk4": _tile(1, 1, 4, 1, 8, 0, 2), "patch_96x27_wk2": _tile(1, 2, 2, 1, 12, 0, 2), "patch_48x27_wk1": _tile(1, 4, 1, 1, 12, 0, 2),
+    "patch_64x64_res": _tile(1, 4, 1, 2, 4, 1, 1), "patch_256_wave_pairs": _tile(2, 1, 2, 2, 4, 0, 1, grid_y=2),
+    "patch_512": _tile(2, 1, 2, 2, 4, 0, 1, grid_y=4), "patch_5x300_forwarded": dict(patch=0),
+    "patch_127x127_2d": _tile(1, 4, 1, 1, 4, 1, 1), "patch_37x150_tiled": _tile(2, 2, 1, 2, 4, 1, 2),
+    "s2_32x64_45x67": _tile(1, 4, 1, 2, 9, 1, 1, S2=1), "s2_64x128_17x31": _tile(2, 2, 1, 2, 5, 1, 1, S2=1),
+    "s2_16x64_8x6": _tile(1, 4, 1, 2, 9, 1, 1, S2=1, n_rounds=1), "s2_256x512_28x50": _tile(4, 1, 1, 2, 3, 1, 1, S2=1, grid_y=2),
+}
+ROOT_TILINGS = {
+    "root_64_28x50": _tile(1, 4, 1, 2, 4, 1, 1, fused=1, ROOT=1), "root_256_children": _tile(4, 1, 1, 2, 4, 0, 1, fused=1, ROOT=1),
+    "root_128_one_child": _tile(2, 2, 1, 2, 6, 0, 2, fused=1, ROOT=1), "root_256_14x25_fallback": _tile(2, 1, 2, 2, 4, 0, 1, fused=0, ROOT=0),
+}
+PROJ_TILINGS = {
+    "proj_96_64": _tile(1, 4, 1, 2, 4, 1, 1, PROJ=1), "proj_320_256": _tile(4, 1, 1, 2, 4, 0, 1, PROJ=1),
+    "proj_256_512": _tile(2, 1, 2, 2, 4, 0, 1, PROJ=1),
+}
+DCN_TILINGS = {
+    "dcn_128_64_ksplit": dict(WC=4, WP=1, RT=1, COAL=1, CT=2, ks=4), "dcn_512_256": dict(WC=4, WP=1, RT=2, COAL=1, CT=2, ks=4),
+    "dcn_64_64_37x70": dict(WC=4, WP=1, RT=1, COAL=1, CT=2, ks=1, tiles=41), "dcn_32_48": dict(WC=4, WP=1, RT=1, COAL=1, CT=2, ks=1, grid_y=1),
+}
+
 # cf_stem_fused (B, C, H, W) and cf_stem_fused_early (B, H, W)
 STEM_CASES = {"stem_16x16": (1, 3, 16, 16, "stem:one_tile"), "stem_34x50": (1, 3, 34, 50, "stem:ragged")}
 EARLY_CASES = {"early_36x52": (1, 36, 52, "stem_early:ragged")}

@@ -680,7 +680,7 @@ def test_conv2d_f16x3_fp32_level_accuracy(dev, B, Ci, Co, H, W, k, stride, act, 
     (2, 128, 128, 30, 26, 1, False, True),    # level3
     (2, 256, 256, 14, 25, 1, True, False),    # small map: K split over wave pairs
     (1, 512, 512, 7, 13, 1, False, False),    # level5: 128-channel blocks, K split over wave pairs
-    (1, 64, 64, 5, 300, 1, False, True),      # too wide for the LDS patch: forwarded to the slot kernel
+    (1, 64, 64, 5, 300, 1, False, True),      # too wide for the flat LDS patch; one round of 8 x 16 tiles at this batch (bs 14+: forwarded to the slot kernel)
     (2, 16, 27, 1, 7, 0, False, True),        # single-row image (every dy != 0 tap is outside)
     (1, 64, 64, 112, 200, 1, True, True),     # level2 at the bench size: 16x16 tiles of one image (2-D patch)
     (2, 32, 27, 127, 127, 0, False, True),    # 2-D patch, last tile row / column one pixel short
@@ -688,7 +688,7 @@ def test_conv2d_f16x3_fp32_level_accuracy(dev, B, Ci, Co, H, W, k, stride, act, 
     (16, 256, 256, 28, 50, 1, True, True),    # level4 at the bench size: 8 waves, 128-pixel runs
     (16, 128, 128, 56, 100, 1, True, True),   # level3 at the bench size: 8 waves, 256-pixel runs
     (1, 128, 128, 112, 200, 1, True, True),   # level3 of a 3x896x1600 input: 8 x 16 tiles (the flat patch does not fit)
-    (2, 128, 128, 37, 150, 1, False, True),   # ... ragged tiles, tiled form as the fallback of the flat one
+    (2, 128, 128, 37, 150, 1, False, True),   # ... ragged tiles: one round of 64-channel 8 x 16 tiles (bs 3+: the tiled form as the fallback of the flat one)
     (1, 256, 256, 56, 100, 1, True, True),    # level4 of a 3x896x1600 input: 4 x 16 tiles, 4 waves
     (8, 256, 256, 56, 100, 1, False, True),   # ... 8 waves (>= 160 tiles of 128 pixels), 8 x 16 tiles
     (1, 512, 512, 30, 110, 1, False, True),   # wide 512-channel map
