@@ -199,6 +199,15 @@ SYMBOLS = {
     "cf_head_bwd_chunk_px": (_i, [_i, _i, _i, _i]),
     "cf_head_backward_dx": (_i, [C.POINTER(HeadTrainArgs), _f, _i, _f, _i, _f]),
     "cf_head_bwd_dx_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "cf_offmask_activate": (_i, [_f, C.c_long, _f]),
+    "cf_conv3x3_bwd_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "cf_conv3x3_bwd_weight": (_i, [_f, _f, _f, _i, _i, _i, _i, _f, _f, _f, C.c_size_t, _f]),
+    "cf_conv3x3_bwd_data": (_i, [_f, _f, _f, _i, _i, _i, _i, _f, _f]),
+    "cf_bn_relu_workspace_bytes": (C.c_size_t, [C.c_long, _i]),
+    "cf_bn_relu_train_forward": (_i, [_f, _f, _f, _f, _f, _i, C.c_float, C.c_float, C.c_long, _i, _f, _f, _f, _f, C.c_size_t, _f]),
+    "cf_bn_relu_backward": (_i, [_f, _f, _f, _f, _f, _f, _i, C.c_long, _i, _f, _f, _f, _f, C.c_size_t, _f]),
+    "cf_upsample_dw_bwd_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "cf_upsample_dw_bwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, C.c_size_t, _f]),
     "cf_upsample_dw": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _f]),
     "cf_maxpool2x2": (_i, [_f, _f, _i, _i, _i, _i, _f]),
     "cf_nchw_to_nhwc4": (_i, [_f, _f, _i, _i, _i, _i, _f]),

@@ -6,7 +6,8 @@ base_model.py:30-53 + detectHeads.py:32-163), same call
 `model(images, pc_hm=None, pc_dep=None, calib=None) -> [dict]` (base_model.py:67-106) with the
 same keys, order, shapes and the `pc_hm_in` view of the caller's `pc_dep`
 (detectHeads.py:172).  Eval mode, and one training mode: the heads on a frozen trunk (MODEL.FREEZE_BACKBONE, `_forward_train`); `forward_trunk` /
-`forward_heads` are its two halves, the second differentiable in a caller's feature map.
+`forward_heads` are its two halves, the second differentiable in a caller's feature map.  `unfreeze_neck()` lets dla_up / ida_up
+learn too (`forward_base` / `forward_neck`, `_forward_train_neck`); the base stays frozen.
 
 Nothing else is shared with the reference's design.  The module is a parameter tree plus an
 *execution plan*: at first call for a given (B,H,W) it lays out every intermediate NHWC buffer in
@@ -258,6 +259,7 @@ class DLASeg(nn.Module):
             for name, p in self.named_parameters():
                 p.requires_grad_(name.startswith("detectHead_0."))
         self._stale = False      # a training forward has run: the packed head weights may lag an optimiser step (eval re-packs)
+        self._neck_train = False  # unfreeze_neck(): dla_up / ida_up learn too (the training forward goes through forward_neck)
         self.eval()
 
     def train(self, mode=True):
@@ -650,6 +652,8 @@ class DLASeg(nn.Module):
             if not self.freezeBackbone:
                 raise NotImplementedError("training: only the frozen-backbone mode is implemented (build the model with "
                                           "MODEL.FREEZE_BACKBONE = True: the heads learn on the frozen trunk); call model.eval()")
+            if self._neck_train:
+                return self._forward_train_neck(x, pc_hm, pc_dep, calib)
             return self._forward_train(x, pc_hm, pc_dep, calib)
         self._repack_if_stale()
         if not x.is_cuda:
@@ -754,7 +758,11 @@ class DLASeg(nn.Module):
         association runs and nothing is normalised in place.  Early fusion: `pc_hm` is the map the six-channel stem reads.
         Deviation from the reference: the frozen trunk always uses the folded running statistics of its BatchNorm layers (the
         reference leaves dla_up / ida_up - and, without MODEL.NORM_EVAL, base - in batch-statistics mode).
-        It is `forward_heads` on `_train_trunk`'s map."""
+        It is `forward_heads` on `_train_trunk`'s map.
+        After `unfreeze_neck()` the training forward is `_forward_train_neck` instead: the base (levels 0-5) stays frozen on the
+        eval plan, dla_up / ida_up run through `forward_neck` (ops.deform_conv_block / ops.upsample_dw_add, NHWC, batch statistics
+        as in the reference) and the heads with their input gradient on, so `loss.backward()` also leaves a gradient on every
+        `dla_up.*` / `ida_up.*` parameter."""
         self._check_train_images(x)
         B, _, H, W = x.shape
         dev = x.device
@@ -767,6 +775,124 @@ class DLASeg(nn.Module):
             # (a copy: autograd keeps the map until backward, the plan's buffer is overwritten by the next forward)
             feat = self._train_trunk(x, pc_hm if self.isEarly else None, B, H, W, dev, sid).clone()
             return self._heads_train(feat, False, pc_hm, pc_dep, calib)
+
+    # ------------------------------------------------------------------------- training: the neck
+    NECK_LEVEL_CHANNELS = (64, 128, 256, 512)
+
+    def unfreeze_neck(self, flag=True):
+        """Let `dla_up.*` / `ida_up.*` learn beside the heads (flag=False: freeze them again): sets their `requires_grad` and
+        selects the neck-training forward for `model.train()` - forward_heads(forward_neck(forward_base(x)), ...) with the heads'
+        input gradient on.  The base (DLA-34 levels 0-5) stays frozen, so this needs MODEL.FREEZE_BACKBONE; without this call
+        every path is what it was.  -> self"""
+        if not self.freezeBackbone:
+            raise NotImplementedError("unfreeze_neck: only with MODEL.FREEZE_BACKBONE = True (the base stays frozen; training the "
+                                      "whole trunk is not implemented)")
+        for name, p in self.named_parameters():
+            if name.startswith(("dla_up.", "ida_up.")):
+                p.requires_grad_(bool(flag))
+        self._neck_train = bool(flag)
+        return self
+
+    def _base_levels(self, x, pc, B, H, W, dev, sid):
+        """the frozen base of a training forward: the eval plan's backbone launches under no_grad -> the NHWC maps of levels 2-5,
+        buffers of the plan (valid until the next call of this shape on this stream)"""
+        with torch.no_grad():
+            p = self._plan((B, H, W, dev, sid, "train-base"), lambda: _Plan(self, B, H, W, dev, part="base"))
+            p.run_trunk(x, pc)
+            return p.levels
+
+    def forward_base(self, images, pc_hm=None):
+        """The frozen base alone: images (B,3,H,W) -> the four level maps the neck reads (levels 2-5: 64, 128, 256, 512 channels at
+        H/4 .. H/32), NCHW, fresh tensors, under no_grad through the eval plan (split-fp16, BatchNorm folded with the running
+        statistics).  Early fusion: `pc_hm` (B,3,H/4,W/4) is the radar map the six-channel stem reads, as in `forward_trunk`."""
+        self._check_train_images(images)
+        B, _, H, W = images.shape
+        dev = images.device
+        x = images.detach().float().contiguous()
+        pc = self._check_train_radar(B, H // 4, W // 4, pc_hm, None) if self.isEarly else None
+        with self._lock, torch.cuda.device(dev):
+            if self._packed is None:
+                self._prepare(dev)
+            sid = torch.cuda.current_stream(dev).cuda_stream
+            with torch.no_grad():
+                return [ops.nhwc_to_nchw(t) for t in self._base_levels(x, pc, B, H, W, dev, sid)]
+
+    def _neck_block(self, p, xn):
+        """one DeformConv of the neck (dla.py:456-472) on the module's own parameters; BatchNorm follows model.training"""
+        g, b = self.get_parameter, self.get_buffer
+        s = (self._scale(p + ".conv_offset_mask"), self._scale(p))
+        y = ops.deform_conv_block_nhwc(xn, g(p + ".conv_offset_mask.weight"), g(p + ".conv_offset_mask.bias"), g(p + ".weight"),
+                                       g(p + ".bias"), g(p + ".activation.0.weight"), g(p + ".activation.0.bias"),
+                                       b(p + ".activation.0.running_mean"), b(p + ".activation.0.running_var"),
+                                       training=self.training, in_scales=None if None in s else s, pack_verify=False)
+        if self.training:
+            b(p + ".activation.0.num_batches_tracked").add_(1)
+        return y
+
+    def _neck_ida(self, p, layers, startp, endp):
+        """IDAUp.forward (dla.py:518-524) through the two operators"""
+        for i in range(startp + 1, endp):
+            j = i - startp
+            up_w = self.get_parameter(f"{p}.up_{j}.weight")
+            proj = self._neck_block(f"{p}.proj_{j}", layers[i])
+            layers[i] = self._neck_block(f"{p}.node_{j}", ops.upsample_dw_add_nhwc(proj, up_w, up_w.shape[-1] // 2, layers[i - 1]))
+
+    def _neck_nhwc(self, levels):
+        """DLAUp.forward + IDAUp.forward (dla.py:553-559, 627-635) on the NHWC maps of levels 2-5 -> the (B,h,w,64) feature map.
+        A plain composition on the caller's stream: no lanes, groups or sub-batch streams."""
+        layers = list(levels)
+        out = [layers[-1]]
+        for i in range(len(layers) - 1):
+            self._neck_ida(f"dla_up.ida_{i}", layers, len(layers) - i - 2, len(layers))
+            out.insert(0, layers[-1])
+        y = out[:3]
+        self._neck_ida("ida_up", y, 0, 3)
+        return y[-1]
+
+    def forward_neck(self, levels):
+        """The reference's neck, `DLAUp.forward` + `IDAUp.forward` (dla.py:518-559, 627-635), on the model's own parameters through
+        `ops.deform_conv_block` and `ops.upsample_dw_add`: `levels` = the four (B,C,h,w) fp32 maps of levels 2-5 (`forward_base`'s,
+        or a caller's own) -> the (B,64,H/4,W/4) feature map, differentiable in every `dla_up.*` / `ida_up.*` parameter that
+        requires grad and in the levels that do.  NHWC inside, on the caller's stream.  BatchNorm follows `model.training`: batch
+        statistics (and the running statistics' update) under `model.train()`, as the reference runs dla_up / ida_up; the running
+        statistics otherwise.  A calibrated model passes its per-layer pre-scales, so no range check and no host sync runs per
+        layer; an uncalibrated one checks each block's input as `ops.deform_conv2d` does.  In training mode the packed weights
+        are marked stale: the next eval forward re-packs with the new weights and running statistics."""
+        levels = list(levels)
+        if len(levels) != 4 or not all(torch.is_tensor(t) and t.is_cuda for t in levels):
+            raise _lib.CfHipError("DLASeg.forward_neck needs the four level maps as device tensors: the HIP path has no CPU fallback")
+        for t, c in zip(levels, self.NECK_LEVEL_CHANNELS):
+            if t.dim() != 4 or t.shape[1] != c or t.dtype != torch.float32:
+                raise ValueError(f"levels must be float32 (B,{c},h,w) maps of levels 2-5, got {t.dtype} {tuple(t.shape)}")
+        if self.use_graph and self.training:
+            raise NotImplementedError("training mode: model.use_graph is not supported (autograd does not record through a captured "
+                                      "graph); set model.use_graph = False")
+        dev = levels[0].device
+        with self._lock, torch.cuda.device(dev):
+            if self._packed is None:
+                self._prepare(dev)
+            if self.training:
+                self._stale = True
+            feat = self._neck_nhwc([ops._to_nhwc(t) for t in levels])
+            return ops._NhwcToNchwFn.apply(feat)
+
+    def _forward_train_neck(self, x, pc_hm, pc_dep, calib):
+        """model.train() after unfreeze_neck(): forward_heads(forward_neck(forward_base(x)), ...) without the layout launches in
+        between - the base on the eval plan under no_grad, the neck and the heads under autograd (NHWC throughout)."""
+        self._check_train_images(x)
+        B, _, H, W = x.shape
+        dev = x.device
+        x = x.detach().float().contiguous()
+        pc_hm = self._check_train_radar(B, H // 4, W // 4, pc_hm, pc_dep)
+        with self._lock, torch.cuda.device(dev):
+            if self._packed is None:
+                self._prepare(dev)
+            sid = torch.cuda.current_stream(dev).cuda_stream
+            # (copies: autograd keeps the maps until backward, the plan's buffers are overwritten by the next forward)
+            levels = [t.clone() for t in self._base_levels(x, pc_hm if self.isEarly else None, B, H, W, dev, sid)]
+            self._stale = True
+            feat = self._neck_nhwc(levels)
+            return self._heads_train(feat, True, pc_hm, pc_dep, calib)
 
     def forward_trunk(self, images, pc_hm=None):
         """The frozen trunk alone: images (B,3,H,W) -> the (B,64,H/4,W/4) NCHW feature map the heads read, under no_grad, a fresh

@@ -463,22 +463,25 @@ def _checksum(weight, bias):
     return c
 
 
-def _packed_dcn(weight, bias):
+def _packed_dcn(weight, bias, pack=None, verify=True):
     """Pack (split fp16 hi / lo, MFMA fragment order: packing.pack_dcn_f16) ONCE per weight tensor OBJECT and content -
     the reference calls the operator with the same nn.Parameter every forward (dla.py:464-465).  The entry holds weak
     references and is valid only while they still point at the very tensors passed in (a data pointer or an id() alone
     can be reused by another tensor after the first one is freed), their version counter, data pointer, shape and dtype
-    are unchanged, and - `set_dcn_pack_verify` - their bits still add up to the checksum taken at packing time."""
+    are unchanged, and - `set_dcn_pack_verify` - their bits still add up to the checksum taken at packing time.
+    `pack` (default packing.pack_dcn_f16): the packer of another layer kind that lives in the same cache - the offset
+    convolution of `deform_conv_block` (a weight tensor is one layer's, so the key stays the weight).  verify=False: this call
+    trusts the version counters (DLASeg's own nn.Parameters, which only optimizers and load_state_dict write): no checksum, no sync."""
     import weakref
     from . import packing
     with _DCN_PACK_LOCK:
-        return _packed_dcn_locked(weight, bias, weakref, packing)
+        return _packed_dcn_locked(weight, bias, weakref, packing, pack, verify)
 
 
-def _packed_dcn_locked(weight, bias, weakref, packing):
+def _packed_dcn_locked(weight, bias, weakref, packing, pack=None, verify=True):
     key = id(weight)
     e = _DCN_PACKS.pop(key, None)
-    verify = _DCN_PACK_VERIFY and weight.is_cuda and not torch.cuda.is_current_stream_capturing()
+    verify = verify and _DCN_PACK_VERIFY and weight.is_cuda and not torch.cuda.is_current_stream_capturing()
     csum = None
     if e is not None:
         wref, wst, bref, bst, pd, csum0 = e
@@ -494,7 +497,7 @@ def _packed_dcn_locked(weight, bias, weakref, packing):
     if e is None:
         w = weight.detach().float().cpu()
         b = torch.zeros(w.shape[0]) if bias is None else bias.detach().float().cpu()
-        pd = packing.pack_dcn_f16(w, b).to(weight.device)
+        pd = (pack or packing.pack_dcn_f16)(w, b).to(weight.device)
         if verify and csum is None:
             csum = int(_checksum(weight, bias).item())
         e = (weakref.ref(weight), _stamp(weight), None if bias is None else weakref.ref(bias),
@@ -629,8 +632,9 @@ def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0
     fixed order and cannot.  At an integer sampling position the offset gradient is the right-hand derivative, as
     torchvision's is.  The range check and the packed-weight cache behave as in inference: an optimizer's in-place step
     bumps the weight's version, so the next forward packs it again.  Otherwise (no_grad, nothing requiring grad) the
-    inference path runs as it always did and the result carries no grad_fn.  The module path (`DLASeg`) never
-    differentiates its trunk (it trains its heads only: `head_stack`)."""
+    inference path runs as it always did and the result carries no grad_fn.  The module path (`DLASeg`) does not come
+    through here: it trains its heads through `head_stack` and, after `unfreeze_neck`, its neck through `deform_conv_block`,
+    which shares this operator's backward kernels and stays NHWC."""
     _need_cuda(input, offset, weight, bias, mask)
     if input.dim() != 4 or weight.dim() != 4:
         raise ValueError("deform_conv2d: input must be (B,Cin,H,W) and weight (Cout,Cin,kh,kw)")
@@ -1012,6 +1016,305 @@ def upsample_dw(x, weight_kkc, f, skip=None, out=None):
                                           out.data_ptr(), B, H, W, Cc, f, _lib.stream_ptr()),
                "cf_upsample_dw")
     return out
+
+
+# ---- the neck under autograd: the DeformConv block and the IDA upsample (csrc/cf_neck_bwd.hip) ----
+def _bytes(n, dev):
+    return torch.empty(max(int(n), 1), device=dev, dtype=torch.uint8)
+
+
+def run_bn_relu_forward(x, gamma, beta, running_mean, running_var, training, momentum, eps):
+    """y = relu(batch_norm(x)) on an NHWC map (cf_bn_relu_train_forward) -> (y, mean, invstd): batch statistics and the
+    running-statistics update with `training`, the running statistics' affine without."""
+    Cc = x.shape[-1]
+    M = x.numel() // Cc
+    y = torch.empty_like(x)
+    mean, invstd = torch.empty(Cc, device=x.device, dtype=torch.float32), torch.empty(Cc, device=x.device, dtype=torch.float32)
+    nbytes = _lib.load().cf_bn_relu_workspace_bytes(M, Cc)
+    ws = _bytes(nbytes, x.device)
+    _lib.check(_lib.load().cf_bn_relu_train_forward(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _lib.ptr(running_mean),
+                                                    _lib.ptr(running_var), int(bool(training)), float(momentum), float(eps), M, Cc,
+                                                    y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), nbytes,
+                                                    _lib.stream_ptr()), "cf_bn_relu_train_forward")
+    return y, mean, invstd
+
+
+def run_bn_relu_backward(gy, x, gamma, beta, mean, invstd, training, want_gz=True, want_gamma=True, want_beta=True):
+    """-> (gz, ggamma, gbeta) of run_bn_relu_forward from the pre-BN map `x` and the saved statistics (cf_bn_relu_backward);
+    None for what is not wanted."""
+    Cc = x.shape[-1]
+    M = x.numel() // Cc
+    gz = torch.empty_like(x) if want_gz else None
+    gg = torch.empty(Cc, device=x.device, dtype=torch.float32) if want_gamma else None
+    gb = torch.empty(Cc, device=x.device, dtype=torch.float32) if want_beta else None
+    nbytes = _lib.load().cf_bn_relu_workspace_bytes(M, Cc)
+    ws = _bytes(nbytes, x.device)
+    _lib.check(_lib.load().cf_bn_relu_backward(gy.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
+                                               invstd.data_ptr(), int(bool(training)), M, Cc, _lib.ptr(gz), _lib.ptr(gg), _lib.ptr(gb),
+                                               ws.data_ptr(), nbytes, _lib.stream_ptr()), "cf_bn_relu_backward")
+    return gz, gg, gb
+
+
+def run_offmask_activate(om):
+    """The mask logits in channels 18..26 of an offset-convolution output (B,H,W,32) -> sigmoid, in place (cf_offmask_activate)."""
+    _lib.check(_lib.load().cf_offmask_activate(om.data_ptr(), om.numel() // 32, _lib.stream_ptr()), "cf_offmask_activate")
+    return om
+
+
+def run_conv3x3_bwd_weight(gom, offmask, x, want_gw=True, want_gbias=True):
+    """-> (gw (27,C,3,3), gbias (27)) of the offset convolution from the DCN backward's gom, the mask derivative folded in on load
+    (cf_conv3x3_bwd_weight); None for what is not wanted."""
+    B, H, W, Cc = x.shape
+    gw = torch.empty((27, Cc, 3, 3), device=x.device, dtype=torch.float32) if want_gw else None
+    gb = torch.empty(27, device=x.device, dtype=torch.float32) if want_gbias else None
+    nbytes = _lib.load().cf_conv3x3_bwd_workspace_bytes(B, H, W, Cc)
+    ws = _bytes(nbytes, x.device)
+    _lib.check(_lib.load().cf_conv3x3_bwd_weight(gom.data_ptr(), offmask.data_ptr(), x.data_ptr(), B, H, W, Cc, _lib.ptr(gw),
+                                                 _lib.ptr(gb), ws.data_ptr(), nbytes, _lib.stream_ptr()), "cf_conv3x3_bwd_weight")
+    return gw, gb
+
+
+def run_conv3x3_bwd_data(gom, offmask, weight, gx):
+    """Adds the offset convolution's input gradient into gx (B,H,W,C), behind cf_dcn_v2_bwd_data on the same stream
+    (cf_conv3x3_bwd_data: a new kernel on the exact fp32 MFMA, not cf_conv2d_fused with a flipped weight - the fold of the mask
+    derivative rides on its operand load)."""
+    B, H, W, Cc = gx.shape
+    _lib.check(_lib.load().cf_conv3x3_bwd_data(gom.data_ptr(), offmask.data_ptr(), weight.data_ptr(), B, H, W, Cc, gx.data_ptr(),
+                                               _lib.stream_ptr()), "cf_conv3x3_bwd_data")
+    return gx
+
+
+def run_upsample_dw_bwd(gout, x, weight_kkc, f, want_gx=True, want_gw=True):
+    """-> (gx (B,H,W,C), gweight [k][k][C]) of `upsample_dw` (cf_upsample_dw_bwd); None for what is not wanted."""
+    B, H, W, Cc = x.shape
+    gx = torch.empty_like(x) if want_gx else None
+    gw = torch.empty_like(weight_kkc) if want_gw else None
+    nbytes = _lib.load().cf_upsample_dw_bwd_workspace_bytes(B, H, W, Cc, f)
+    ws = _bytes(nbytes, x.device)
+    _lib.check(_lib.load().cf_upsample_dw_bwd(gout.data_ptr(), x.data_ptr(), weight_kkc.data_ptr(), B, H, W, Cc, f, _lib.ptr(gx),
+                                              _lib.ptr(gw), ws.data_ptr(), nbytes, _lib.stream_ptr()), "cf_upsample_dw_bwd")
+    return gx, gw
+
+
+def _pack_offset_conv(w, b):
+    from . import packing
+    return packing.pack_conv_f16(w, b, [packing.Source(w.shape[1], w.shape[1])])
+
+
+def _f32c(t):
+    t = t.detach()
+    return t if t.is_contiguous() else t.contiguous()
+
+
+class _DeformConvBlockFn(torch.autograd.Function):
+    """`deform_conv_block` under autograd.  Saved: the block input, the offmask buffer with the ACTIVATED mask, the pre-BN map
+    and the batch statistics, the raw weights.  Backward: cf_bn_relu_backward, cf_dcn_v2_bwd_data / _weight,
+    cf_conv3x3_bwd_weight / _data - each only when `needs_input_grad` asks for one of its outputs."""
+
+    @staticmethod
+    def forward(ctx, xn, com_w, com_b, w, b, gamma, beta, packs, stats, training, momentum, eps, scales):
+        pc, pd = packs
+        B, H, W, Cin = xn.shape
+        dev = xn.device
+        with torch.cuda.device(dev):
+            x = _f32c(xn)
+            om = torch.empty((B, H, W, 32), device=dev, dtype=torch.float32)
+            a = conv_args(pc, [x], [Cin], B, H, W, om, 32, ACT_NONE, None, 0, LAYOUT_NHWC, None, 0, False,
+                          in_scale=None if scales is None else scales[0])
+            run_conv_f16(a, pc.patch)
+            run_offmask_activate(om)                   # (the backward reads the activated mask; the DCN takes it as it is)
+            z = torch.empty((B, H, W, pd.n), device=dev, dtype=torch.float32)
+            nbytes = _lib.load().cf_dcn_v2_workspace_bytes(B, H, W, pd.c, pd.n_pad)
+            ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+            d = dcn_args(pd, x, om, 32, B, H, W, z, pd.n, ACT_NONE, precise=True, workspace=ws,
+                         in_scale=None if scales is None else scales[1])
+            d.mask_activated = 1
+            run_dcn(d)
+            g, be = _f32c(gamma), _f32c(beta)
+            y, mean, invstd = run_bn_relu_forward(z, g, be, stats[0], stats[1], training, momentum, eps)
+        ctx.training = bool(training)
+        ctx.save_for_backward(x, om, z, mean, invstd, _f32c(com_w), _f32c(w), g, be)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, om, z, mean, invstd, com_w, w, gamma, beta = ctx.saved_tensors
+        need_x, need_cw, need_cb, need_w, need_b, need_g, need_be = ctx.needs_input_grad[:7]
+        B, H, W, Cin = x.shape
+        dev = x.device
+        gx = gcw = gcb = gw = gb = None
+        with torch.cuda.device(dev):
+            gy = _f32c(gy)
+            upstream = need_x or need_cw or need_cb or need_w or need_b
+            gz, gg, gbe = run_bn_relu_backward(gy, z, gamma, beta, mean, invstd, ctx.training, upstream, need_g, need_be)
+            if need_x or need_cw or need_cb:
+                gx = torch.zeros((B, H, W, Cin), device=dev, dtype=torch.float32) if need_x else None
+                gom = torch.empty((B, H, W, 32), device=dev, dtype=torch.float32)
+                run_dcn_bwd_data(dcn_bwd_args(gz, x, om, weight=w, gx=gx, gom=gom))
+                if need_cw or need_cb:
+                    gcw, gcb = run_conv3x3_bwd_weight(gom, om, x, need_cw, need_cb)
+                if need_x:
+                    run_conv3x3_bwd_data(gom, om, com_w, gx)
+            if need_w or need_b:
+                gw = torch.empty_like(w) if need_w else None
+                gb = torch.empty(w.shape[0], device=dev, dtype=torch.float32) if need_b else None
+                nbytes = _lib.load().cf_dcn_v2_bwd_workspace_bytes(B, H, W, Cin, w.shape[0])
+                wsb = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+                run_dcn_bwd_weight(dcn_bwd_args(gz, x, om, gw=gw, gbias=gb, workspace=wsb))
+        return (gx, gcw, gcb, gw, gb, gg, gbe, None, None, None, None, None, None)
+
+
+def _block_check(who, x, cin, com_weight, com_bias, weight, bias, bn_weight, bn_bias, running_mean, running_var):
+    for t in (x, com_weight, com_bias, weight, bias, bn_weight, bn_bias, running_mean, running_var):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise NotImplementedError(f"{who}: float32 tensors only (no autocast, no fp16 / bf16 / float64)")
+    if x.dim() != 4 or weight.dim() != 4:
+        raise ValueError(f"{who}: x must be a 4-D map and weight (Cout,Cin,3,3)")
+    cout = weight.shape[0]
+    if tuple(weight.shape) != (cout, cin, 3, 3) or tuple(com_weight.shape) != (27, cin, 3, 3):
+        raise NotImplementedError(f"{who}: weight must be (Cout,{cin},3,3) and the offset convolution's (27,{cin},3,3) - 3x3, stride 1, "
+                                  f"padding 1, one group, one offset group only - got {tuple(weight.shape)} / {tuple(com_weight.shape)}")
+    if cin % 32 or cout % 32 or cin > 512 or cout > 1024:
+        raise NotImplementedError(f"{who}: Cin={cin} (at most 512) and Cout={cout} (at most 1024) must be multiples of 32")
+    for t, n, what in ((com_bias, 27, "com_bias"), (bias, cout, "bias"), (bn_weight, cout, "bn_weight"), (bn_bias, cout, "bn_bias"),
+                       (running_mean, cout, "running_mean"), (running_var, cout, "running_var")):
+        if tuple(t.shape) != (n,):
+            raise ValueError(f"{who}: {what} must be ({n},), got {tuple(t.shape)}")
+    _need_cuda(x, com_weight, com_bias, weight, bias, bn_weight, bn_bias, running_mean, running_var)
+
+
+def deform_conv_block_nhwc(xn, com_weight, com_bias, weight, bias, bn_weight, bn_bias, running_mean, running_var, training=True,
+                           momentum=0.1, eps=1e-5, in_scales=None, pack_verify=True):
+    """`deform_conv_block` on a map that is already NHWC: xn (B,H,W,Cin) -> (B,H,W,Cout).  The neck of DLASeg's training
+    forward composes these (and `upsample_dw_add_nhwc`) without a layout launch in between.  pack_verify=False: the packed-weight
+    cache trusts the weights' version counters for this call (`set_dcn_pack_verify` explains the checksum it skips)."""
+    _block_check("deform_conv_block", xn, xn.shape[-1] if torch.is_tensor(xn) and xn.dim() == 4 else -1, com_weight, com_bias, weight,
+                 bias, bn_weight, bn_bias, running_mean, running_var)
+    B, H, W, _ = xn.shape
+    if training and B * H * W == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {(B, weight.shape[0], H, W)}")
+    if in_scales is not None:
+        scales = (float(in_scales[0]), float(in_scales[1]))
+    elif _DCN_RANGE_CHECK and not torch.cuda.is_current_stream_capturing():
+        with torch.cuda.device(xn.device):
+            s = in_scale_for(float(absmax(_f32c(xn)).item()))          # (raises on NaN / inf)
+        scales = (s, s)
+    else:
+        scales = None
+    packs = (_packed_dcn(com_weight, com_bias, pack=_pack_offset_conv, verify=pack_verify), _packed_dcn(weight, bias, verify=pack_verify))
+    return _DeformConvBlockFn.apply(xn, com_weight, com_bias, weight, bias, bn_weight, bn_bias, packs, (running_mean, running_var),
+                                    bool(training), float(momentum), float(eps), scales)
+
+
+class _NhwcToNchwFn(torch.autograd.Function):
+    """The layout conversion behind an NCHW-outside operator: cf_nhwc_to_nchw forward, cf_nchw_to_nhwc backward."""
+
+    @staticmethod
+    def forward(ctx, x):
+        with torch.cuda.device(x.device):
+            return nhwc_to_nchw(x.detach().contiguous())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        with torch.cuda.device(g.device):
+            return nchw_to_nhwc(g.detach().contiguous())
+
+
+def _to_nhwc(t):
+    if torch.is_grad_enabled() and t.requires_grad:
+        return _NchwToNhwcFn.apply(t)
+    with torch.no_grad(), torch.cuda.device(t.device):
+        return nchw_to_nhwc(t.contiguous())
+
+
+def deform_conv_block(x, com_weight, com_bias, weight, bias, bn_weight, bn_bias, running_mean, running_var, training=True,
+                      momentum=0.1, eps=1e-5, in_scales=None):
+    """The reference's `DeformConv(activation=True).forward` (model/networks/dla.py:456-472) as ONE operator under autograd, on HIP
+    kernels in both directions: conv_offset_mask (3x3, Cin -> 27) -> chunk / cat / sigmoid -> modulated deformable 3x3 convolution
+    -> BatchNorm2d -> ReLU.  `x` (B,Cin,H,W) fp32 on the device -> (B,Cout,H,W); com_weight (27,Cin,3,3), com_bias (27), weight
+    (Cout,Cin,3,3), bias (Cout), bn_weight / bn_bias / running_mean / running_var (Cout); Cin and Cout multiples of 32.
+
+    Forward: the split-fp16 offset convolution (cf_conv3x3_f16x3) and cf_dcn_v2_f16x3 on weights packed once per weight version
+    (the cache of `deform_conv2d`, which also holds the offset convolution's), then cf_bn_relu_train_forward.  `training=True`:
+    batch statistics (two-pass variance), running_mean / running_var updated in place with `momentum` and the unbiased variance
+    as torch.nn.BatchNorm2d does (num_batches_tracked is the caller's); one value per channel raises ValueError.
+    `training=False`: the affine of the running statistics, still differentiable.  The range check is `deform_conv2d`'s: with
+    `set_dcn_range_check` on, every call measures max |x| (one device -> host scalar) and picks the pre-scale; `in_scales` =
+    (offset convolution's, DCN's) pre-scales skips it - no check, no host sync.
+
+    Differentiable once in x and the six parameters; only the launches `needs_input_grad` asks for run.  Parameter gradients are
+    slab sums added in a fixed order (bitwise reproducible); the input gradient goes through the DCN's float atomics.  CPU tensors
+    raise CfHipError, non-fp32 tensors and unsupported shapes NotImplementedError."""
+    _block_check("deform_conv_block", x, x.shape[1] if torch.is_tensor(x) and x.dim() == 4 else -1, com_weight, com_bias, weight, bias,
+                 bn_weight, bn_bias, running_mean, running_var)
+    y = deform_conv_block_nhwc(_to_nhwc(x), com_weight, com_bias, weight, bias, bn_weight, bn_bias, running_mean, running_var,
+                               training, momentum, eps, in_scales)
+    return _NhwcToNchwFn.apply(y)
+
+
+class _UpsampleDwAddFn(torch.autograd.Function):
+    """`upsample_dw_add` under autograd: cf_upsample_dw forward; cf_upsample_dw_bwd backward (the skip's gradient is gout)."""
+
+    @staticmethod
+    def forward(ctx, xn, weight, f, skipn):
+        with torch.cuda.device(xn.device):
+            x, skip = _f32c(xn), _f32c(skipn)
+            wk = weight.detach()[:, 0].permute(1, 2, 0).contiguous()        # (C,1,k,k) -> [k][k][C]
+            out = upsample_dw(x, wk, f, skip)
+        ctx.f = f
+        ctx.save_for_backward(x, wk)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        x, wk = ctx.saved_tensors
+        need_x, need_w, _, need_s = ctx.needs_input_grad
+        gx = gw = None
+        gout = _f32c(gout)
+        if need_x or need_w:
+            with torch.cuda.device(x.device):
+                gx, gwk = run_upsample_dw_bwd(gout, x, wk, ctx.f, need_x, need_w)
+                if need_w:
+                    gw = gwk.permute(2, 0, 1).unsqueeze(1).contiguous()
+        return gx, gw, None, (gout if need_s else None)
+
+
+def _upsample_check(x, weight, f, skip, c, hw, skip_hw):
+    for t in (x, weight, skip):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise NotImplementedError("upsample_dw_add: float32 tensors only (no autocast, no fp16 / bf16 / float64)")
+    if f not in (2, 4):
+        raise NotImplementedError(f"upsample_dw_add: f={f!r} (2 or 4 only: k = 2f, stride f, padding f/2)")
+    if tuple(weight.shape) != (c, 1, 2 * f, 2 * f) or c % 4:
+        raise NotImplementedError(f"upsample_dw_add: weight must be the depthwise ({c},1,{2 * f},{2 * f}) with C a multiple of 4, "
+                                  f"got {tuple(weight.shape)}")
+    if tuple(skip_hw) != (hw[0] * f, hw[1] * f):
+        raise ValueError(f"upsample_dw_add: skip must be the x{f} map of x, got {tuple(skip.shape)} for {tuple(x.shape)}")
+    _need_cuda(x, weight, skip)
+
+
+def upsample_dw_add_nhwc(xn, weight, f, skipn):
+    """`upsample_dw_add` on NHWC maps: xn (B,H,W,C), skipn (B,H*f,W*f,C) -> (B,H*f,W*f,C)."""
+    if not (torch.is_tensor(xn) and torch.is_tensor(skipn) and xn.dim() == 4 and skipn.dim() == 4 and skipn.shape[0] == xn.shape[0]
+            and skipn.shape[3] == xn.shape[3]):
+        raise ValueError("upsample_dw_add: x and skip must be 4-D maps of one batch and channel count")
+    _upsample_check(xn, weight, f, skipn, xn.shape[3], xn.shape[1:3], skipn.shape[1:3])
+    return _UpsampleDwAddFn.apply(xn, weight, int(f), skipn)
+
+
+def upsample_dw_add(x, weight, f, skip):
+    """One IDA step of the reference (model/networks/dla.py:518-524): `up(x) + skip`, `up` the depthwise
+    ConvTranspose2d(C, C, 2f, stride=f, padding=f/2, groups=C, bias=False) with `weight` (C,1,2f,2f), f = 2 or 4; x (B,C,H,W) and
+    skip (B,C,H*f,W*f) fp32 on the device.  Forward cf_upsample_dw (the add fused), backward cf_upsample_dw_bwd; differentiable
+    once in x, weight and skip (skip's gradient is the output gradient itself).  The weight gradient is a slab sum added in a
+    fixed order: bitwise reproducible."""
+    if not (torch.is_tensor(x) and torch.is_tensor(skip) and x.dim() == 4 and skip.dim() == 4 and skip.shape[:2] == x.shape[:2]):
+        raise ValueError("upsample_dw_add: x and skip must be 4-D maps of one batch and channel count")
+    _upsample_check(x, weight, f, skip, x.shape[1], x.shape[2:], skip.shape[2:])
+    return _NhwcToNchwFn.apply(upsample_dw_add_nhwc(_to_nhwc(x), weight, f, _to_nhwc(skip)))
 
 
 def maxpool2x2(x, out=None):

@@ -34,6 +34,7 @@ class _Plan:
 
     def __init__(self, model: "DLASeg", B, H, W, device, part="all", feat=None, feat_in=None):
         """part: "all" (one plan per forward), or the two halves of the split forward (DLASeg.streams > 1):
+        "base" = the backbone alone, run like a trunk (run_trunk), its level 2-5 maps kept in `levels` (DLASeg.forward_base);
         "trunk" = backbone + neck of a sub-batch, its last DCN writing the feature map (and its split-bf16 copy)
         into the caller's `feat` / `feat_in` slices; "heads" = everything behind the feature map for the WHOLE
         batch, reading the full `feat` / `feat_in` buffers the trunks filled."""
@@ -85,7 +86,7 @@ class _Plan:
         try:                                         # (model -> _plans -> plan -> model would leave a dropped plan set to the collector)
             if part != "heads":
                 self._build_trunk()
-            if part != "trunk":
+            if part not in ("trunk", "base"):
                 self._build_heads()
         finally:
             self._m = self._pk = None
@@ -344,6 +345,9 @@ class _Plan:
         for lvl, levels, root in ((2, 1, False), (3, 2, True), (4, 2, True), (5, 1, True)):
             layers.append(self._tree(f"base.level{lvl}", levels, layers[-1], 2, root))
         self.debug = {f"y{i}": t for i, t in enumerate(layers) if t is not None}
+        if self.part == "base":
+            self.levels = layers[2:]                 # levels 2-5: what the neck reads (DLASeg.forward_base)
+            return
         # ---- DLA-up + IDA-up neck
         out = [layers[-1]]
         n_ida = len(layers) - 2 - 1

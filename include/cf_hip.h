@@ -451,6 +451,51 @@ int cf_dcn_v2_bwd_data(const cf_dcn_bwd_args* a, void* stream);
 int cf_dcn_v2_bwd_weight(const cf_dcn_bwd_args* a, void* stream);
 size_t cf_dcn_v2_bwd_workspace_bytes(int B, int H, int W, int C, int N);
 
+/* Training kernels of the neck's DeformConv block (conv_offset_mask -> sigmoid -> DCN -> BatchNorm -> ReLU,
+ * model/networks/dla.py:456-472) and of the IDA upsample (added within ABI 7: nothing existing changed).  All tensors
+ * fp32 NHWC.  Every parameter gradient is a sum of slab partials that a second launch adds in slab order: bitwise
+ * reproducible, no float atomics.  Products through MFMA use the exact fp32-input MFMA: no range to guard.
+ *
+ * cf_conv3x3_bwd_weight / cf_conv3x3_bwd_data: backward of the offset convolution (3x3, stride 1, zero padding 1,
+ * C -> 27; C a multiple of 32, at most 512).  gom [B][H][W][32] is cf_dcn_v2_bwd_data's: channels 18..26 are the
+ * gradient with respect to the ACTIVATED mask m, which offmask [B][H][W][32] holds; both kernels multiply them by
+ * m (1 - m) as they load them (the gradient with respect to the logits the convolution produced), channels 27..31 are
+ * ignored.  _weight: gw [27][C][3][3] and gbias [27], either may be NULL (both: nothing runs); x [B][H][W][C] is the
+ * convolution's input.  _data ADDS the input gradient into gx [B][H][W][C] (plain read-modify-write, each pixel row
+ * owned by one workgroup: run it on the stream of, and behind, cf_dcn_v2_bwd_data, which fills gx); weight is the raw
+ * [27][C][3][3]. */
+/* cf_offmask_activate: channels 18..26 of an offmask buffer [M][32] in place, logit -> sigmoid: the forward of the block keeps
+ * the ACTIVATED mask (cf_dcn_args.mask_activated = 1), which the backward kernels read. */
+int cf_offmask_activate(float* offmask, long M, void* stream);
+size_t cf_conv3x3_bwd_workspace_bytes(int B, int H, int W, int C);
+int cf_conv3x3_bwd_weight(const float* gom, const float* offmask, const float* x, int B, int H, int W, int C, float* gw,
+                          float* gbias, void* workspace, size_t workspace_bytes, void* stream);
+int cf_conv3x3_bwd_data(const float* gom, const float* offmask, const float* weight, int B, int H, int W, int C, float* gx,
+                        void* stream);
+
+/* cf_bn_relu_train_forward: y = relu(gamma (x - mean) invstd + beta) on an [M][C] map (M = B*H*W rows; C a multiple of
+ * 4, at most 1024).  training != 0: mean and the biased variance of the batch - per slab of rows the mean about a
+ * pivot row and the sum of squares about that mean (two passes), the slabs merged in slab order in float64 - and
+ * running_mean / running_var (either may be NULL) updated with `momentum`, the latter with the unbiased M / (M - 1)
+ * variance; M = 1 is refused.  training == 0: mean / invstd of the running statistics.  save_mean / save_invstd [C]
+ * are written for the backward.  cf_bn_relu_backward: from gy, the same x (the pre-BN map), gamma, beta and the saved
+ * statistics: gz [M][C], ggamma [C], gbeta [C]; each may be NULL.  The ReLU mask is recomputed with the forward's own
+ * expression.  The workspace of both is cf_bn_relu_workspace_bytes(M, C). */
+size_t cf_bn_relu_workspace_bytes(long M, int C);
+int cf_bn_relu_train_forward(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                             int training, float momentum, float eps, long M, int C, float* y, float* save_mean,
+                             float* save_invstd, void* workspace, size_t workspace_bytes, void* stream);
+int cf_bn_relu_backward(const float* gy, const float* x, const float* gamma, const float* beta, const float* save_mean,
+                        const float* save_invstd, int training, long M, int C, float* gz, float* ggamma, float* gbeta,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* cf_upsample_dw_bwd: backward of cf_upsample_dw for f = 2 or 4 (k = 2f).  gout [B][H*f][W*f][C]; gx [B][H][W][C] is
+ * gathered from the k x k block of gout each input pixel fed; gweight in the packed [k][k][C] order (x is read for it
+ * only).  Either output may be NULL.  The skip input's gradient is gout itself. */
+size_t cf_upsample_dw_bwd_workspace_bytes(int B, int H, int W, int C, int f);
+int cf_upsample_dw_bwd(const float* gout, const float* x, const float* weight, int B, int H, int W, int C, int f, float* gx,
+                       float* gweight, void* workspace, size_t workspace_bytes, void* stream);
+
 /* cf_upsample_dw: depthwise transposed conv (k = 2f, stride f, pad f/2, groups = C, no bias),
  * optionally fused with the IDA skip add:  out = convT(x) [+ skip].
  * replaces aten::conv_transpose2d + add of model/networks/dla.py:502-511, 518-524.

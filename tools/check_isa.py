@@ -18,6 +18,7 @@ SOURCES = {"cf_conv3x3_f16.hip": ("conv3x3_f16x3_kernel",), "cf_heads.hip": ("he
            "cf_gemm_f16.hip": ("dcn_f16x3_kernel", "conv_f16x3_kernel"), "cf_frustum.hip": ("pc_hm_direct_kernel",),
            "cf_stem_early.hip": ("stem_early_kernel",),
            "cf_dcn_bwd.hip": ("dcn_bwd_data_kernel", "dcn_bwd_weight_kernel"),
+           "cf_neck_bwd.hip": ("conv3x3_bwd_data_kernel", "conv3x3_bwd_weight_kernel"),
            "cf_targets.hip": ("targets_heat_kernel", "targets_frustum_kernel")}
 
 
@@ -57,7 +58,10 @@ EPILOGUE_KERNELS = ("conv_f16x3_kernel", "dcn_f16x3_kernel", "conv3x3_f16x3_kern
 # kernels of the default path: NO instantiation may use scratch at all (ScratchSize 0 in the compiler's resource summary)
 NO_SCRATCH = ("head_patch16_kernel", "dcn_f16x3_kernel", "conv3x3_f16x3_kernel", "conv_f16x3_kernel",
               "pc_hm_direct_kernel", "stem_early_kernel", "dcn_bwd_data_kernel", "dcn_bwd_weight_kernel", "dcn_bwd_reduce_kernel",
-              "targets_object_kernel", "targets_heat_kernel", "targets_frustum_kernel")
+              "targets_object_kernel", "targets_heat_kernel", "targets_frustum_kernel",
+              "offmask_activate_kernel", "conv3x3_bwd_weight_kernel", "conv3x3_bwd_reduce_kernel", "conv3x3_bwd_data_kernel", "bn_stats_kernel",
+              "bn_finalize_kernel", "bn_relu_apply_kernel", "bn_bwd_partial_kernel", "bn_bwd_finalize_kernel", "bn_bwd_apply_kernel",
+              "upsample_bwd_x_kernel", "upsample_bwd_w_kernel", "upsample_bwd_reduce_kernel")
 
 
 def scratch_sizes(asm):
