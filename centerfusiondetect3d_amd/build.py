@@ -26,6 +26,7 @@ SOURCES = [
     ("cf_gemm_f16.hip", []),
     ("cf_dcn_bwd.hip", []),
     ("cf_neck_bwd.hip", []),
+    ("cf_base_bwd.hip", []),
     ("cf_conv3x3_f16.hip", []),
     ("cf_stem.hip", []),
     ("cf_stem_early.hip", []),

@@ -7,7 +7,8 @@ base_model.py:30-53 + detectHeads.py:32-163), same call
 same keys, order, shapes and the `pc_hm_in` view of the caller's `pc_dep`
 (detectHeads.py:172).  Eval mode, and one training mode: the heads on a frozen trunk (MODEL.FREEZE_BACKBONE, `_forward_train`); `forward_trunk` /
 `forward_heads` are its two halves, the second differentiable in a caller's feature map.  `unfreeze_neck()` lets dla_up / ida_up
-learn too (`forward_base` / `forward_neck`, `_forward_train_neck`); the base stays frozen.
+learn too (`forward_base` / `forward_neck`, `_forward_train_neck`); `unfreeze_base()` adds the base's levels 2-5 (`forward_stem` /
+`forward_levels`, `_forward_train_base`); the stem stays frozen.
 
 Nothing else is shared with the reference's design.  The module is a parameter tree plus an
 *execution plan*: at first call for a given (B,H,W) it lays out every intermediate NHWC buffer in
@@ -260,6 +261,7 @@ class DLASeg(nn.Module):
                 p.requires_grad_(name.startswith("detectHead_0."))
         self._stale = False      # a training forward has run: the packed head weights may lag an optimiser step (eval re-packs)
         self._neck_train = False  # unfreeze_neck(): dla_up / ida_up learn too (the training forward goes through forward_neck)
+        self._base_train = False  # unfreeze_base(): base levels 2-5 learn too (the training forward goes through forward_levels)
         self.eval()
 
     def train(self, mode=True):
@@ -652,6 +654,8 @@ class DLASeg(nn.Module):
             if not self.freezeBackbone:
                 raise NotImplementedError("training: only the frozen-backbone mode is implemented (build the model with "
                                           "MODEL.FREEZE_BACKBONE = True: the heads learn on the frozen trunk); call model.eval()")
+            if self._base_train:
+                return self._forward_train_base(x, pc_hm, pc_dep, calib)
             if self._neck_train:
                 return self._forward_train_neck(x, pc_hm, pc_dep, calib)
             return self._forward_train(x, pc_hm, pc_dep, calib)
@@ -892,6 +896,137 @@ class DLASeg(nn.Module):
             levels = [t.clone() for t in self._base_levels(x, pc_hm if self.isEarly else None, B, H, W, dev, sid)]
             self._stale = True
             feat = self._neck_nhwc(levels)
+            return self._heads_train(feat, True, pc_hm, pc_dep, calib)
+
+    # ------------------------------------------------------------------------- training: the base, levels 2-5
+    def unfreeze_base(self, flag=True):
+        """Let the DLA-34 base from level 2 upward (`base.level2.*` .. `base.level5.*`, nearly all of the base's parameters) learn
+        beside the neck and the heads (flag=False: freeze base and neck again): implies `unfreeze_neck(flag)`, sets their
+        `requires_grad` and selects the base-training forward for `model.train()` -
+        forward_heads(forward_neck(forward_levels(forward_stem(x))), ...).  Needs MODEL.FREEZE_BACKBONE, like `unfreeze_neck`;
+        without this call every path is what it was.
+        Deviation from the reference: the stem stays frozen.  `base.base_layer`, `level0` and `level1` (the 7x7 convolution and the
+        16 / 32-channel layers: a fraction of a percent of the base's parameters) keep running on the eval stem kernel with their
+        folded running statistics and receive no gradient.  -> self"""
+        if not self.freezeBackbone:
+            raise NotImplementedError("unfreeze_base: only with MODEL.FREEZE_BACKBONE = True (the stem stays frozen; training the "
+                                      "whole trunk is not implemented)")
+        self.unfreeze_neck(flag)
+        for name, p in self.named_parameters():
+            if name.startswith(("base.level2.", "base.level3.", "base.level4.", "base.level5.")):
+                p.requires_grad_(bool(flag))
+        self._base_train = bool(flag)
+        return self
+
+    def _stem_map(self, x, pc, B, H, W, dev, sid):
+        """the frozen stem of a training forward: the eval plan's stem launch under no_grad -> the (B, H/2, W/2, 32) NHWC map of
+        level 1, a buffer of the plan (valid until the next call of this shape on this stream)"""
+        with torch.no_grad():
+            p = self._plan((B, H, W, dev, sid, "train-stem"), lambda: _Plan(self, B, H, W, dev, part="stem"))
+            p.run_trunk(x, pc)
+            return p.levels[0]
+
+    def forward_stem(self, images, pc_hm=None):
+        """The frozen stem alone (`base.base_layer`, `level0`, `level1`): images (B,3,H,W) -> the (B,32,H/2,W/2) map of level 1,
+        NCHW, a fresh tensor, under no_grad through the eval plan (split-fp16, BatchNorm folded with the running statistics).
+        Early fusion: `pc_hm` (B,3,H/4,W/4) is the radar map the six-channel stem reads, as in `forward_base`."""
+        self._check_train_images(images)
+        B, _, H, W = images.shape
+        dev = images.device
+        x = images.detach().float().contiguous()
+        pc = self._check_train_radar(B, H // 4, W // 4, pc_hm, None) if self.isEarly else None
+        with self._lock, torch.cuda.device(dev):
+            if self._packed is None:
+                self._prepare(dev)
+            sid = torch.cuda.current_stream(dev).cuda_stream
+            with torch.no_grad():
+                return ops.nhwc_to_nchw(self._stem_map(x, pc, B, H, W, dev, sid))
+
+    def _cba(self, name, conv, bn, x, stride=1, residual=None, relu=True):
+        """one conv + BatchNorm block of the base on the module's own parameters; BatchNorm follows model.training"""
+        g, b = self.get_parameter, self.get_buffer
+        y = ops.conv_bn_act_nhwc(x, g(conv + ".weight"), g(bn + ".weight"), g(bn + ".bias"), b(bn + ".running_mean"),
+                                 b(bn + ".running_var"), stride=stride, residual=residual, relu=relu, training=self.training,
+                                 in_scale=self._scale(name), pack_verify=False)
+        if self.training:
+            b(bn + ".num_batches_tracked").add_(1)
+        return y
+
+    def _lv_block(self, p, x, stride, residual):
+        """BasicBlock.forward (dla.py:144-161)"""
+        t = self._cba(p + ".conv1", p + ".conv1", p + ".bn1", x, stride=stride)
+        return self._cba(p + ".conv2", p + ".conv2", p + ".bn2", t, residual=x if residual is None else residual)
+
+    def _lv_tree(self, p, levels, x, stride, level_root, children=None, pooled=None):
+        """Tree.forward (dla.py:104-118); a nested Tree computes its own residual (the outer Trees of levels 3 and 4 have no project).
+        pooled: the 2x2 max-pool of x where the enclosing Tree has taken it already (both pool the same tensor: one launch)."""
+        children = [] if children is None else children
+        bottom = pooled if pooled is not None else (ops.max_pool2x2_nhwc(x) if stride > 1 else x)
+        if (p + ".project.0.weight") in self._base_names:
+            residual = self._cba(p + ".project", p + ".project.0", p + ".project.1", bottom, relu=False)
+        else:
+            residual = bottom
+        if level_root:
+            children.append(bottom)
+        if levels > 1:
+            x1 = self._lv_tree(p + ".tree1", levels - 1, x, stride, False, pooled=bottom if stride > 1 else None)
+            children.append(x1)
+            return self._lv_tree(p + ".tree2", levels - 1, x1, 1, False, children)
+        x1 = self._lv_block(p + ".tree1", x, stride, residual)
+        x2 = self._lv_block(p + ".tree2", x1, 1, None)
+        # Root.forward (dla.py:36-42; residual_root is False for DLA-34): one 1x1 block over the channel concat, autograd splits
+        return self._cba(p + ".root", p + ".root.conv", p + ".root.bn", torch.cat([x2, x1, *children], dim=3))
+
+    def _levels_nhwc(self, y1):
+        """DLA.forward's levels 2-5 (dla.py:225-232) on the NHWC map of level 1 -> the four NHWC level maps"""
+        self._base_names = {n for n, _ in self.named_parameters() if n.startswith("base.")}
+        out, x = [], y1
+        for lvl, levels, root in ((2, 1, False), (3, 2, True), (4, 2, True), (5, 1, True)):
+            x = self._lv_tree(f"base.level{lvl}", levels, x, 2, root)
+            out.append(x)
+        return out
+
+    def forward_levels(self, level1):
+        """The reference's `DLA.forward` from level 2 upward (dla.py:44-118, 121-161, 193-232) on the model's own parameters through
+        `ops.conv_bn_act` and `ops.max_pool2x2`: `level1` = the (B,32,h,w) fp32 map of level 1 (`forward_stem`'s, or a caller's
+        own; h, w multiples of 16) -> the four level maps (64, 128, 256, 512 channels at h/2 .. h/16), NCHW, differentiable in
+        every `base.level[2-5].*` parameter that requires grad and in `level1` if that does.  NHWC inside, on the caller's stream.
+        BatchNorm follows `model.training`: batch statistics with the running statistics updated in the kernel and
+        `num_batches_tracked` incremented here, the running statistics otherwise.  A calibrated model passes its per-layer
+        pre-scales (no range check, no host sync); an uncalibrated one checks each block's input as `ops.deform_conv2d` does.  In
+        training mode the packed weights are marked stale: the next eval forward re-packs and equals a fresh model loaded from
+        the `state_dict`."""
+        if not torch.is_tensor(level1) or not level1.is_cuda:
+            raise _lib.CfHipError("DLASeg.forward_levels needs a device tensor: the HIP path has no CPU fallback")
+        if level1.dim() != 4 or level1.shape[1] != 32 or level1.dtype != torch.float32 or level1.shape[2] % 16 or level1.shape[3] % 16:
+            raise ValueError(f"level1 must be a float32 (B,32,h,w) map with h, w multiples of 16, got {level1.dtype} {tuple(level1.shape)}")
+        if self.use_graph and self.training:
+            raise NotImplementedError("training mode: model.use_graph is not supported (autograd does not record through a captured "
+                                      "graph); set model.use_graph = False")
+        with self._lock, torch.cuda.device(level1.device):
+            if self._packed is None:
+                self._prepare(level1.device)
+            if self.training:
+                self._stale = True
+            return [ops._NhwcToNchwFn.apply(t) for t in self._levels_nhwc(ops._to_nhwc(level1))]
+
+    def _forward_train_base(self, x, pc_hm, pc_dep, calib):
+        """model.train() after unfreeze_base(): forward_heads(forward_neck(forward_levels(forward_stem(x))), ...) without the layout
+        launches in between - the stem on the eval plan under no_grad, levels 2-5, the neck and the heads under autograd (NHWC
+        throughout)."""
+        self._check_train_images(x)
+        B, _, H, W = x.shape
+        dev = x.device
+        x = x.detach().float().contiguous()
+        pc_hm = self._check_train_radar(B, H // 4, W // 4, pc_hm, pc_dep)
+        with self._lock, torch.cuda.device(dev):
+            if self._packed is None:
+                self._prepare(dev)
+            sid = torch.cuda.current_stream(dev).cuda_stream
+            # (a copy: autograd keeps the map until backward, the plan's buffer is overwritten by the next forward)
+            y1 = self._stem_map(x, pc_hm if self.isEarly else None, B, H, W, dev, sid).clone()
+            self._stale = True
+            feat = self._neck_nhwc(self._levels_nhwc(y1))
             return self._heads_train(feat, True, pc_hm, pc_dep, calib)
 
     def forward_trunk(self, images, pc_hm=None):

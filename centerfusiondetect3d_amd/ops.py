@@ -1317,6 +1317,251 @@ def upsample_dw_add(x, weight, f, skip):
     return _NhwcToNchwFn.apply(upsample_dw_add_nhwc(_to_nhwc(x), weight, f, _to_nhwc(skip)))
 
 
+# ---- the base under autograd: the conv + BatchNorm block and the 2x2 max-pool (csrc/cf_base_bwd.hip) ----
+def conv_out_hw(H, W, k, stride):
+    """(Ho, Wo) of a k x k convolution with padding (k - 1) / 2"""
+    pad = (k - 1) // 2
+    return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+
+def run_conv_bwd_weight(gz, x, k, stride=1):
+    """-> gw (N,C,k,k) of a k x k convolution (padding (k-1)/2, no bias) from gz (B,Ho,Wo,N) and its input x (B,H,W,C), NHWC
+    (cf_conv_bwd_weight: slab partials added in slab order)."""
+    B, H, W, Cc = x.shape
+    N = gz.shape[-1]
+    gw = torch.empty((N, Cc, k, k), device=x.device, dtype=torch.float32)
+    nbytes = _lib.load().cf_conv_bwd_workspace_bytes(B, H, W, Cc, N, k, stride)
+    ws = _bytes(nbytes, x.device)
+    _lib.check(_lib.load().cf_conv_bwd_weight(gz.data_ptr(), x.data_ptr(), B, H, W, Cc, N, k, stride, gw.data_ptr(), ws.data_ptr(),
+                                              nbytes, _lib.stream_ptr()), "cf_conv_bwd_weight")
+    return gw
+
+
+def run_conv_bwd_data(gz, weight, H, W, stride=1):
+    """-> gx (B,H,W,C) of a k x k convolution from gz (B,Ho,Wo,N) and the raw weight (N,C,k,k) (cf_conv_bwd_data: a kernel of its
+    own on the exact fp32 MFMA that reads the torch weight as it is - nothing to re-pack behind an optimizer step)."""
+    B = gz.shape[0]
+    N, Cc, k, _ = weight.shape
+    gx = torch.empty((B, H, W, Cc), device=gz.device, dtype=torch.float32)
+    _lib.check(_lib.load().cf_conv_bwd_data(gz.data_ptr(), weight.data_ptr(), B, H, W, Cc, N, k, stride, gx.data_ptr(),
+                                            _lib.stream_ptr()), "cf_conv_bwd_data")
+    return gx
+
+
+def run_bn_act_forward(x, gamma, beta, running_mean, running_var, training, momentum, eps, residual=None, relu=True):
+    """y = act(batch_norm(x) [+ residual]) on an NHWC map (cf_bn_act_train_forward) -> (y, mean, invstd); act = ReLU or nothing.
+    residual=None, relu=True: the bits of `run_bn_relu_forward`."""
+    Cc = x.shape[-1]
+    M = x.numel() // Cc
+    y = torch.empty_like(x)
+    mean, invstd = torch.empty(Cc, device=x.device, dtype=torch.float32), torch.empty(Cc, device=x.device, dtype=torch.float32)
+    nbytes = _lib.load().cf_bn_act_workspace_bytes(M, Cc)
+    ws = _bytes(nbytes, x.device)
+    _lib.check(_lib.load().cf_bn_act_train_forward(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _lib.ptr(residual), int(bool(relu)),
+                                                   _lib.ptr(running_mean), _lib.ptr(running_var), int(bool(training)), float(momentum),
+                                                   float(eps), M, Cc, y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(),
+                                                   nbytes, _lib.stream_ptr()), "cf_bn_act_train_forward")
+    return y, mean, invstd
+
+
+def run_bn_act_backward(gy, x, gamma, beta, mean, invstd, training, residual=None, relu=True, want_gz=True, want_gres=True,
+                        want_gamma=True, want_beta=True):
+    """-> (gz, gres, ggamma, gbeta) of run_bn_act_forward from the pre-BN map `x`, the residual the forward added and the saved
+    statistics (cf_bn_act_backward); None for what is not wanted."""
+    Cc = x.shape[-1]
+    M = x.numel() // Cc
+    gz = torch.empty_like(x) if want_gz else None
+    gr = torch.empty_like(x) if want_gres else None
+    gg = torch.empty(Cc, device=x.device, dtype=torch.float32) if want_gamma else None
+    gb = torch.empty(Cc, device=x.device, dtype=torch.float32) if want_beta else None
+    nbytes = _lib.load().cf_bn_act_workspace_bytes(M, Cc)
+    ws = _bytes(nbytes, x.device)
+    _lib.check(_lib.load().cf_bn_act_backward(gy.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _lib.ptr(residual),
+                                              int(bool(relu)), mean.data_ptr(), invstd.data_ptr(), int(bool(training)), M, Cc,
+                                              _lib.ptr(gz), _lib.ptr(gr), _lib.ptr(gg), _lib.ptr(gb), ws.data_ptr(), nbytes,
+                                              _lib.stream_ptr()), "cf_bn_act_backward")
+    return gz, gr, gg, gb
+
+
+def run_maxpool2x2_bwd(gout, x):
+    """-> gx (B,H,W,C) of `maxpool2x2` from gout (B,H/2,W/2,C) and the pooled map x (cf_maxpool2x2_bwd: the first maximum of a
+    window in row-major order takes the gradient, as aten's does)."""
+    B, H, W, Cc = x.shape
+    gx = torch.empty_like(x)
+    _lib.check(_lib.load().cf_maxpool2x2_bwd(gout.data_ptr(), x.data_ptr(), B, H, W, Cc, gx.data_ptr(), _lib.stream_ptr()),
+               "cf_maxpool2x2_bwd")
+    return gx
+
+
+def _packed_conv(weight, stride, verify=True):
+    """the raw convolution weight (no bias, no BN fold) packed for the split-fp16 kernels, once per weight version: the cache of
+    `deform_conv2d`.  A 3x3's slice-major packing is the same for stride 1 and 2; the entry carries the stride it was packed for."""
+    import dataclasses
+    from . import packing
+
+    def pack(w, b):
+        return packing.pack_conv_f16(w, b, [packing.Source(w.shape[1], w.shape[1])], stride=stride)
+    pc = _packed_dcn(weight, None, pack=pack, verify=verify)
+    return pc if pc.stride == stride else dataclasses.replace(pc, stride=stride)
+
+
+class _ConvBnActFn(torch.autograd.Function):
+    """`conv_bn_act` under autograd.  Saved: the block input, the pre-BN map, the residual only where the ReLU mask needs it, the
+    batch statistics, the raw weight.  Backward: cf_bn_act_backward, then cf_conv_bwd_weight / cf_conv_bwd_data - each only when
+    `needs_input_grad` asks for its output."""
+
+    @staticmethod
+    def forward(ctx, xn, w, gamma, beta, resn, pc, stats, stride, relu, training, momentum, eps, scale):
+        B, H, W, _ = xn.shape
+        with torch.cuda.device(xn.device):
+            x = _f32c(xn)
+            res = None if resn is None else _f32c(resn)
+            z = conv2d_f16x3(pc, [x], B, H, W, ACT_NONE, in_scale=scale)
+            g, be = _f32c(gamma), _f32c(beta)
+            y, mean, invstd = run_bn_act_forward(z, g, be, stats[0], stats[1], training, momentum, eps, res, relu)
+        ctx.training, ctx.relu, ctx.stride, ctx.has_res = bool(training), bool(relu), int(stride), res is not None
+        ctx.save_for_backward(x, z, mean, invstd, _f32c(w), g, be, *([res] if res is not None and relu else []))
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, z, mean, invstd, w, gamma, beta, *rest = ctx.saved_tensors
+        res = rest[0] if rest else None
+        need_x, need_w, need_g, need_be, need_r = ctx.needs_input_grad[:5]
+        need_r = need_r and ctx.has_res
+        _, H, W, _ = x.shape
+        gx = gw = gres = None
+        with torch.cuda.device(x.device):
+            gy = _f32c(gy)
+            gz, gres, gg, gbe = run_bn_act_backward(gy, z, gamma, beta, mean, invstd, ctx.training, res, ctx.relu, need_x or need_w,
+                                                    need_r and ctx.relu, need_g, need_be)
+            if need_r and not ctx.relu:
+                gres = gy                              # (no mask: the residual's gradient is the output's)
+            if need_w:
+                gw = run_conv_bwd_weight(gz, x, w.shape[-1], ctx.stride)
+            if need_x:
+                gx = run_conv_bwd_data(gz, w, H, W, ctx.stride)
+        return (gx, gw, gg, gbe, gres, None, None, None, None, None, None, None, None)
+
+
+def _conv_bn_check(who, x, cin, hw, weight, bn_weight, bn_bias, running_mean, running_var, stride, residual, res_shape):
+    for t in (x, weight, bn_weight, bn_bias, running_mean, running_var) + (() if residual is None else (residual,)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise NotImplementedError(f"{who}: float32 tensors only (no autocast, no fp16 / bf16 / float64)")
+    if x.dim() != 4 or weight.dim() != 4:
+        raise ValueError(f"{who}: x must be a 4-D map and weight (Cout,Cin,k,k)")
+    cout, k = weight.shape[0], weight.shape[2]
+    if tuple(weight.shape) != (cout, cin, k, k) or k not in (1, 3) or stride not in (1, 2) or (stride == 2 and k != 3):
+        raise NotImplementedError(f"{who}: weight must be (Cout,{cin},k,k) with k = 1 (stride 1) or k = 3 (stride 1 or 2), padding "
+                                  f"(k-1)/2, one group - got {tuple(weight.shape)}, stride {stride!r}")
+    if cin % 32 or cout % 32 or cin > 1280 or cout > 512:
+        raise NotImplementedError(f"{who}: Cin={cin} (at most 1280) and Cout={cout} (at most 512) must be multiples of 32")
+    for t, what in ((bn_weight, "bn_weight"), (bn_bias, "bn_bias"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if tuple(t.shape) != (cout,):
+            raise ValueError(f"{who}: {what} must be ({cout},), got {tuple(t.shape)}")
+    ho, wo = conv_out_hw(hw[0], hw[1], k, stride)
+    if residual is not None and tuple(res_shape) != (x.shape[0], cout, ho, wo):
+        raise ValueError(f"{who}: residual must have the output's shape {(x.shape[0], cout, ho, wo)}")
+    _need_cuda(x, weight, bn_weight, bn_bias, running_mean, running_var, residual)
+    return ho, wo
+
+
+def conv_bn_act_nhwc(xn, weight, bn_weight, bn_bias, running_mean, running_var, stride=1, residual=None, relu=True, training=True,
+                     momentum=0.1, eps=1e-5, in_scale=None, pack_verify=True):
+    """`conv_bn_act` on maps that are already NHWC: xn (B,H,W,Cin), residual (B,Ho,Wo,Cout) or None -> (B,Ho,Wo,Cout).
+    DLASeg.forward_levels composes these (and `max_pool2x2_nhwc`) without a layout launch in between.  pack_verify=False: the
+    packed-weight cache trusts the weight's version counter for this call (`set_dcn_pack_verify`)."""
+    ok = torch.is_tensor(xn) and xn.dim() == 4
+    ho, wo = _conv_bn_check("conv_bn_act", xn, xn.shape[-1] if ok else -1, xn.shape[1:3] if ok else (0, 0), weight, bn_weight, bn_bias,
+                            running_mean, running_var, stride, residual,
+                            () if residual is None or residual.dim() != 4 else (residual.shape[0], residual.shape[3], *residual.shape[1:3]))
+    if training and xn.shape[0] * ho * wo == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {(xn.shape[0], weight.shape[0], ho, wo)}")
+    if in_scale is not None:
+        scale = float(in_scale)
+    elif _DCN_RANGE_CHECK and not torch.cuda.is_current_stream_capturing():
+        with torch.cuda.device(xn.device):
+            scale = in_scale_for(float(absmax(_f32c(xn)).item()))          # (raises on NaN / inf)
+    else:
+        scale = None
+    pc = _packed_conv(weight, int(stride), verify=pack_verify)
+    return _ConvBnActFn.apply(xn, weight, bn_weight, bn_bias, residual, pc, (running_mean, running_var), int(stride), bool(relu),
+                              bool(training), float(momentum), float(eps), scale)
+
+
+def conv_bn_act(x, weight, bn_weight, bn_bias, running_mean, running_var, stride=1, residual=None, relu=True, training=True,
+                momentum=0.1, eps=1e-5, in_scale=None):
+    """The block shape of the reference's DLA-34 base (model/networks/dla.py:44-118, 121-161) as ONE operator under autograd, on HIP
+    kernels in both directions: Conv2d(k, stride, padding (k-1)/2, bias=False) -> BatchNorm2d -> [+ residual] -> [ReLU].
+    BasicBlock.conv1 is (relu), BasicBlock.conv2 (residual, relu), Tree.project a 1x1 without ReLU, Root a 1x1 (relu) over a
+    channel concat.  `x` (B,Cin,H,W) fp32 on the device -> (B,Cout,Ho,Wo); weight (Cout,Cin,k,k) with k = 3 (stride 1 or 2) or
+    k = 1 (stride 1); bn_weight / bn_bias / running_mean / running_var (Cout); residual None or of the output's shape; Cin
+    (at most 1280) and Cout (at most 512) multiples of 32.
+
+    Forward: the split-fp16 convolution (cf_conv3x3_f16x3 / cf_conv2d_f16x3) on the raw weight - no BN fold - packed once per
+    weight version (the cache of `deform_conv2d`), then cf_bn_act_train_forward.  `training=True`: batch statistics, running_mean
+    / running_var updated in place as torch.nn.BatchNorm2d does (num_batches_tracked is the caller's); one value per channel
+    raises ValueError.  `training=False`: the affine of the running statistics, still differentiable.  The range check is
+    `deform_conv2d`'s: with `set_dcn_range_check` on, every call measures max |x| (one device -> host scalar) and picks the
+    pre-scale; `in_scale` skips it - no check, no host sync.
+
+    Differentiable once in x, weight, bn_weight, bn_bias and residual; only the launches `needs_input_grad` asks for run:
+    cf_bn_act_backward, then cf_conv_bwd_weight and cf_conv_bwd_data on the exact fp32 MFMA.  Every gradient is bitwise
+    reproducible (no float atomics).  CPU tensors raise CfHipError, non-fp32 tensors and unsupported shapes NotImplementedError."""
+    ok = torch.is_tensor(x) and x.dim() == 4
+    _conv_bn_check("conv_bn_act", x, x.shape[1] if ok else -1, x.shape[2:] if ok else (0, 0), weight, bn_weight, bn_bias, running_mean,
+                   running_var, stride, residual, () if residual is None else tuple(residual.shape))
+    y = conv_bn_act_nhwc(_to_nhwc(x), weight, bn_weight, bn_bias, running_mean, running_var, stride,
+                         None if residual is None else _to_nhwc(residual), relu, training, momentum, eps, in_scale)
+    return _NhwcToNchwFn.apply(y)
+
+
+class _MaxPool2x2Fn(torch.autograd.Function):
+    """`max_pool2x2` under autograd: cf_maxpool2x2 forward, cf_maxpool2x2_bwd backward."""
+
+    @staticmethod
+    def forward(ctx, xn):
+        with torch.cuda.device(xn.device):
+            x = _f32c(xn)
+            out = maxpool2x2(x)
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        x, = ctx.saved_tensors
+        with torch.cuda.device(x.device):
+            return run_maxpool2x2_bwd(_f32c(gout), x)
+
+
+def _pool_check(x, c, hw):
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise NotImplementedError("max_pool2x2: float32 tensors only (no autocast, no fp16 / bf16 / float64)")
+    if x.dim() != 4:
+        raise ValueError("max_pool2x2: x must be a 4-D map")
+    if c % 4 or hw[0] < 2 or hw[1] < 2:
+        raise NotImplementedError(f"max_pool2x2: C={c} must be a multiple of 4 and the map at least 2 x 2, got {tuple(x.shape)}")
+    _need_cuda(x)
+
+
+def max_pool2x2_nhwc(xn):
+    """`max_pool2x2` on an NHWC map: (B,H,W,C) -> (B,H/2,W/2,C)."""
+    ok = torch.is_tensor(xn) and xn.dim() == 4
+    _pool_check(xn, xn.shape[3] if ok else 0, xn.shape[1:3] if ok else (0, 0))
+    return _MaxPool2x2Fn.apply(xn)
+
+
+def max_pool2x2(x):
+    """F.max_pool2d(x, 2, 2) (Tree.downsample, dla.py:96,107) under autograd: x (B,C,H,W) fp32 on the device -> (B,C,H/2,W/2).
+    Forward cf_maxpool2x2, backward cf_maxpool2x2_bwd: the whole gradient of a window goes to its first maximum in row-major
+    order - aten's choice on a tie, and post-ReLU maps are full of all-zero windows.  `maxpool2x2` is the plain NHWC launch."""
+    ok = torch.is_tensor(x) and x.dim() == 4
+    _pool_check(x, x.shape[1] if ok else 0, x.shape[2:] if ok else (0, 0))
+    return _NhwcToNchwFn.apply(max_pool2x2_nhwc(_to_nhwc(x)))
+
+
 def maxpool2x2(x, out=None):
     _need_cuda(x)
     B, H, W, Cc = x.shape

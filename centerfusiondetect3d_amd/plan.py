@@ -35,6 +35,8 @@ class _Plan:
     def __init__(self, model: "DLASeg", B, H, W, device, part="all", feat=None, feat_in=None):
         """part: "all" (one plan per forward), or the two halves of the split forward (DLASeg.streams > 1):
         "base" = the backbone alone, run like a trunk (run_trunk), its level 2-5 maps kept in `levels` (DLASeg.forward_base);
+        "stem" = base_layer + level0 + level1 alone, run like a trunk, the (B, H/2, W/2, 32) map of level 1 in `levels`
+        (DLASeg.forward_stem; early fusion: the six-channel stem);
         "trunk" = backbone + neck of a sub-batch, its last DCN writing the feature map (and its split-bf16 copy)
         into the caller's `feat` / `feat_in` slices; "heads" = everything behind the feature map for the WHOLE
         batch, reading the full `feat` / `feat_in` buffers the trunks filled."""
@@ -86,7 +88,7 @@ class _Plan:
         try:                                         # (model -> _plans -> plan -> model would leave a dropped plan set to the collector)
             if part != "heads":
                 self._build_trunk()
-            if part not in ("trunk", "base"):
+            if part not in ("trunk", "base", "stem"):
                 self._build_heads()
         finally:
             self._m = self._pk = None
@@ -322,7 +324,7 @@ class _Plan:
             # base_layer + level0 + level1 in one launch; the full-resolution maps stay in LDS
             y0, y1 = None, self._buf(B, H // 2, W // 2, 32)
             # ... and the level-2 Tree's 2x2 max-pool of that map (dla.py:96) comes out of the same launch
-            y1p = self._buf(B, H // 4, W // 4, 32) if m.stem_pool else None
+            y1p = self._buf(B, H // 4, W // 4, 32) if m.stem_pool and self.part != "stem" else None
             if y1p is not None:
                 self._pooled[y1.data_ptr()] = y1p
             stem_layers = ("base.base_layer", "base.level0", "base.level1")
@@ -342,6 +344,9 @@ class _Plan:
             y0 = self._conv("base.level0", [t], H, W)
             y1 = self._conv("base.level1", [y0], H, W)
         layers = [y0, y1]
+        if self.part == "stem":
+            self.levels = [y1]                       # level 1: what DLASeg.forward_levels reads (DLASeg.forward_stem)
+            return
         for lvl, levels, root in ((2, 1, False), (3, 2, True), (4, 2, True), (5, 1, True)):
             layers.append(self._tree(f"base.level{lvl}", levels, layers[-1], 2, root))
         self.debug = {f"y{i}": t for i, t in enumerate(layers) if t is not None}

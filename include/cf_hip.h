@@ -496,6 +496,47 @@ size_t cf_upsample_dw_bwd_workspace_bytes(int B, int H, int W, int C, int f);
 int cf_upsample_dw_bwd(const float* gout, const float* x, const float* weight, int B, int H, int W, int C, int f, float* gx,
                        float* gweight, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Training kernels of the DLA-34 base, levels 2-5 (added within ABI 7: nothing existing changed).  One block shape covers
+ * them: convolution (no bias) -> BatchNorm -> [+ residual] -> [ReLU] (model/networks/dla.py:44-118, 121-161).  All
+ * tensors fp32 NHWC; products through the exact fp32-input MFMA: no range to guard, nothing is clamped.  No float
+ * atomics: every output is bitwise reproducible.
+ *
+ * Geometry of the two convolution kernels: k = 1 or 3, padding (k - 1) / 2, stride 1 or 2 (2 with k = 3 only),
+ * Ho = (H + 2 pad - k) / stride + 1 (odd H, W are fine under stride 2); C and N multiples of 32, C <= 1280, N <= 512.
+ * x [B][H][W][C] is the convolution's input, gz [B][Ho][Wo][N] the gradient of its output, weight the raw torch
+ * [N][C][k][k] (no host packing on the backward path).
+ * cf_conv_bwd_weight: gw [N][C][k][k].  The output pixels are split into slabs whose partial sums (workspace:
+ * cf_conv_bwd_workspace_bytes(...)) a second launch adds in slab order.
+ * cf_conv_bwd_data: gx [B][H][W][C], plain stores of every element (no accumulate-into form); each pixel row of gx is
+ * owned by one workgroup.  Under stride 2 a workgroup's pixels share their row / column parity and its tap loop walks
+ * the taps of that parity alone (no zero-stuffed gz). */
+size_t cf_conv_bwd_workspace_bytes(int B, int H, int W, int C, int N, int k, int stride);
+int cf_conv_bwd_weight(const float* gz, const float* x, int B, int H, int W, int C, int N, int k, int stride, float* gw,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int cf_conv_bwd_data(const float* gz, const float* weight, int B, int H, int W, int C, int N, int k, int stride,
+                     float* gx, void* stream);
+
+/* cf_bn_act_train_forward: y = act(gamma (x - mean) invstd + beta [+ residual]) on an [M][C] map; residual NULL or
+ * [M][C], relu 0 or 1 (act = ReLU or nothing).  Statistics, running-statistics update, the float64 slab merge and the
+ * workspace are cf_bn_relu_train_forward's (the same kernels): with residual == NULL and relu == 1 the results equal
+ * cf_bn_relu_* bit for bit.  cf_bn_act_backward: gz [M][C] (the pre-BN map's gradient), gres [M][C] (the residual's:
+ * gy under the ReLU mask), ggamma [C], gbeta [C]; each may be NULL.  The ReLU mask is recomputed from the forward's
+ * own expression, residual included; the per-channel sums are slab partials added in slab order. */
+size_t cf_bn_act_workspace_bytes(long M, int C);
+int cf_bn_act_train_forward(const float* x, const float* gamma, const float* beta, const float* residual, int relu,
+                            float* running_mean, float* running_var, int training, float momentum, float eps, long M,
+                            int C, float* y, float* save_mean, float* save_invstd, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int cf_bn_act_backward(const float* gy, const float* x, const float* gamma, const float* beta, const float* residual,
+                       int relu, const float* save_mean, const float* save_invstd, int training, long M, int C,
+                       float* gz, float* gres, float* ggamma, float* gbeta, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* cf_maxpool2x2_bwd: backward of cf_maxpool2x2.  gout [B][H/2][W/2][C], x [B][H][W][C] the pooled map, gx [B][H][W][C]:
+ * the whole gradient goes to the first maximum of each window in row-major order (what aten does on a tie); every
+ * element of gx is written, zeros included.  C a multiple of 4; no workspace. */
+int cf_maxpool2x2_bwd(const float* gout, const float* x, int B, int H, int W, int C, float* gx, void* stream);
+
 /* cf_upsample_dw: depthwise transposed conv (k = 2f, stride f, pad f/2, groups = C, no bias),
  * optionally fused with the IDA skip add:  out = convT(x) [+ skip].
  * replaces aten::conv_transpose2d + add of model/networks/dla.py:502-511, 518-524.
