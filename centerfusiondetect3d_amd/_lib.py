@@ -216,6 +216,10 @@ SYMBOLS = {
     "cf_bn_act_train_forward": (_i, [_f, _f, _f, _f, _i, _f, _f, _i, C.c_float, C.c_float, C.c_long, _i, _f, _f, _f, _f, C.c_size_t, _f]),
     "cf_bn_act_backward": (_i, [_f, _f, _f, _f, _f, _i, _f, _f, _i, C.c_long, _i, _f, _f, _f, _f, _f, C.c_size_t, _f]),
     "cf_maxpool2x2_bwd": (_i, [_f, _f, _i, _i, _i, _i, _f, _f]),
+    "cf_stem_conv_bwd_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
+    "cf_stem_conv_forward": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f, _f]),
+    "cf_stem_conv_bwd_weight": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f, _f, C.c_size_t, _f]),
+    "cf_stem_conv_bwd_data": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _i, _f, _f]),
     "cf_maxpool2x2": (_i, [_f, _f, _i, _i, _i, _i, _f]),
     "cf_nchw_to_nhwc4": (_i, [_f, _f, _i, _i, _i, _i, _f]),
     "cf_nhwc_to_nchw": (_i, [_f, _f, _i, _i, _i, _i, _i, _f]),

@@ -27,6 +27,7 @@ SOURCES = [
     ("cf_dcn_bwd.hip", []),
     ("cf_neck_bwd.hip", []),
     ("cf_base_bwd.hip", []),
+    ("cf_stem_train.hip", []),
     ("cf_conv3x3_f16.hip", []),
     ("cf_stem.hip", []),
     ("cf_stem_early.hip", []),

@@ -8,7 +8,8 @@ same keys, order, shapes and the `pc_hm_in` view of the caller's `pc_dep`
 (detectHeads.py:172).  Eval mode, and one training mode: the heads on a frozen trunk (MODEL.FREEZE_BACKBONE, `_forward_train`); `forward_trunk` /
 `forward_heads` are its two halves, the second differentiable in a caller's feature map.  `unfreeze_neck()` lets dla_up / ida_up
 learn too (`forward_base` / `forward_neck`, `_forward_train_neck`); `unfreeze_base()` adds the base's levels 2-5 (`forward_stem` /
-`forward_levels`, `_forward_train_base`); the stem stays frozen.
+`forward_levels`, `_forward_train_base`); the stem stays frozen unless `unfreeze_stem()` (`forward_stem_train`), after which every
+parameter learns.
 
 Nothing else is shared with the reference's design.  The module is a parameter tree plus an
 *execution plan*: at first call for a given (B,H,W) it lays out every intermediate NHWC buffer in
@@ -262,6 +263,7 @@ class DLASeg(nn.Module):
         self._stale = False      # a training forward has run: the packed head weights may lag an optimiser step (eval re-packs)
         self._neck_train = False  # unfreeze_neck(): dla_up / ida_up learn too (the training forward goes through forward_neck)
         self._base_train = False  # unfreeze_base(): base levels 2-5 learn too (the training forward goes through forward_levels)
+        self._stem_train = False  # unfreeze_stem(): the stem learns too (the base-training forward runs forward_stem_train's blocks)
         self.eval()
 
     def train(self, mode=True):
@@ -653,7 +655,9 @@ class DLASeg(nn.Module):
         if self.training:
             if not self.freezeBackbone:
                 raise NotImplementedError("training: only the frozen-backbone mode is implemented (build the model with "
-                                          "MODEL.FREEZE_BACKBONE = True: the heads learn on the frozen trunk); call model.eval()")
+                                          "MODEL.FREEZE_BACKBONE = True: the heads learn on the frozen trunk, unfreeze_neck() / "
+                                          "unfreeze_base() / unfreeze_stem() add the rest - unfreeze_stem() trains every "
+                                          "parameter); call model.eval()")
             if self._base_train:
                 return self._forward_train_base(x, pc_hm, pc_dep, calib)
             if self._neck_train:
@@ -905,9 +909,10 @@ class DLASeg(nn.Module):
         `requires_grad` and selects the base-training forward for `model.train()` -
         forward_heads(forward_neck(forward_levels(forward_stem(x))), ...).  Needs MODEL.FREEZE_BACKBONE, like `unfreeze_neck`;
         without this call every path is what it was.
-        Deviation from the reference: the stem stays frozen.  `base.base_layer`, `level0` and `level1` (the 7x7 convolution and the
-        16 / 32-channel layers: a fraction of a percent of the base's parameters) keep running on the eval stem kernel with their
-        folded running statistics and receive no gradient.  -> self"""
+        Deviation from the reference, unless `unfreeze_stem()`: the stem stays frozen.  `base.base_layer`, `level0` and `level1`
+        (the 7x7 convolution and the 16 / 32-channel layers: a fraction of a percent of the base's parameters) keep running on
+        the eval stem kernel with their folded running statistics and receive no gradient; `unfreeze_stem()` trains them too.
+        -> self"""
         if not self.freezeBackbone:
             raise NotImplementedError("unfreeze_base: only with MODEL.FREEZE_BACKBONE = True (the stem stays frozen; training the "
                                       "whole trunk is not implemented)")
@@ -916,6 +921,11 @@ class DLASeg(nn.Module):
             if name.startswith(("base.level2.", "base.level3.", "base.level4.", "base.level5.")):
                 p.requires_grad_(bool(flag))
         self._base_train = bool(flag)
+        if not flag and self._stem_train:                # (a stem that learns under a frozen base is no mode of this model)
+            for name, p in self.named_parameters():
+                if name.startswith(("base.base_layer.", "base.level0.", "base.level1.")):
+                    p.requires_grad_(False)
+            self._stem_train = False
         return self
 
     def _stem_map(self, x, pc, B, H, W, dev, sid):
@@ -941,6 +951,59 @@ class DLASeg(nn.Module):
             sid = torch.cuda.current_stream(dev).cuda_stream
             with torch.no_grad():
                 return ops.nhwc_to_nchw(self._stem_map(x, pc, B, H, W, dev, sid))
+
+    # ------------------------------------------------------------------------- training: the stem
+    STEM_LAYERS = (("base.base_layer", 1), ("base.level0", 1), ("base.level1", 2))
+
+    def unfreeze_stem(self, flag=True):
+        """Let the stem (`base.base_layer.*`, `base.level0.*`, `base.level1.*`) learn too, so that every parameter of the model
+        trains as in the reference's normal run (flag=False: freeze stem, base and neck again): implies `unfreeze_base(flag)`,
+        sets the stem parameters' `requires_grad` and makes the base-training forward run the stem through
+        `ops.stem_conv_bn_relu` under autograd (`forward_stem_train`) - batch statistics, running statistics updated - instead
+        of the eval stem kernel.  An early-fusion model then learns its radar input through `base.base_layer.0.weight[:, 3:6]`.
+        Needs MODEL.FREEZE_BACKBONE, like its siblings; without this call every path is what it was.  -> self"""
+        if not self.freezeBackbone:
+            raise NotImplementedError("unfreeze_stem: only with MODEL.FREEZE_BACKBONE = True (build the model frozen, then call "
+                                      "unfreeze_stem(): that is the full-training mode)")
+        self.unfreeze_base(flag)
+        for name, p in self.named_parameters():
+            if name.startswith(("base.base_layer.", "base.level0.", "base.level1.")):
+                p.requires_grad_(bool(flag))
+        self._stem_train = bool(flag)
+        return self
+
+    def _stem_train_nhwc(self, x, pc):
+        """DLA.forward's base_layer, level0, level1 (dla.py:225-228) on the module's own parameters: the NCHW image (and, early
+        fusion, the radar map) -> the (B, H/2, W/2, 32) NHWC map of level 1; BatchNorm follows model.training"""
+        g, b = self.get_parameter, self.get_buffer
+        t = x
+        for i, (p, stride) in enumerate(self.STEM_LAYERS):
+            t = ops.stem_conv_bn_relu_nhwc(t, g(p + ".0.weight"), g(p + ".1.weight"), g(p + ".1.bias"), b(p + ".1.running_mean"),
+                                           b(p + ".1.running_var"), stride=stride, training=self.training,
+                                           radar=pc if i == 0 else None)
+            if self.training:
+                b(p + ".1.num_batches_tracked").add_(1)
+        return t
+
+    def forward_stem_train(self, images, pc_hm=None):
+        """The differentiable twin of `forward_stem`: images (B,3,H,W) -> the (B,32,H/2,W/2) map of level 1, NCHW, through three
+        `ops.stem_conv_bn_relu` blocks on the model's own parameters (exact fp32 on the raw weights, NHWC inside, on the caller's
+        stream), differentiable in every `base.base_layer.*` / `level0.*` / `level1.*` parameter that requires grad.  Early
+        fusion: `pc_hm` (B,3,H/4,W/4) is the radar map the six-channel first layer samples; neither it nor the images receive a
+        gradient.  BatchNorm follows `model.training`: batch statistics with the running statistics updated in the kernel and
+        `num_batches_tracked` incremented here, the running statistics otherwise.  In training mode the packed weights are
+        marked stale: the next eval forward re-packs and equals a fresh model loaded from the `state_dict`."""
+        self._check_train_images(images)
+        B, _, H, W = images.shape
+        dev = images.device
+        x = images.detach().float().contiguous()
+        pc = self._check_train_radar(B, H // 4, W // 4, pc_hm, None) if self.isEarly else None
+        with self._lock, torch.cuda.device(dev):
+            if self._packed is None:
+                self._prepare(dev)
+            if self.training:
+                self._stale = True
+            return ops._NhwcToNchwFn.apply(self._stem_train_nhwc(x, pc))
 
     def _cba(self, name, conv, bn, x, stride=1, residual=None, relu=True):
         """one conv + BatchNorm block of the base on the module's own parameters; BatchNorm follows model.training"""
@@ -1013,7 +1076,7 @@ class DLASeg(nn.Module):
     def _forward_train_base(self, x, pc_hm, pc_dep, calib):
         """model.train() after unfreeze_base(): forward_heads(forward_neck(forward_levels(forward_stem(x))), ...) without the layout
         launches in between - the stem on the eval plan under no_grad, levels 2-5, the neck and the heads under autograd (NHWC
-        throughout)."""
+        throughout).  After unfreeze_stem() the stem runs under autograd too (`_stem_train_nhwc`, forward_stem_train's body)."""
         self._check_train_images(x)
         B, _, H, W = x.shape
         dev = x.device
@@ -1023,8 +1086,11 @@ class DLASeg(nn.Module):
             if self._packed is None:
                 self._prepare(dev)
             sid = torch.cuda.current_stream(dev).cuda_stream
-            # (a copy: autograd keeps the map until backward, the plan's buffer is overwritten by the next forward)
-            y1 = self._stem_map(x, pc_hm if self.isEarly else None, B, H, W, dev, sid).clone()
+            if self._stem_train:
+                y1 = self._stem_train_nhwc(x, pc_hm if self.isEarly else None)
+            else:
+                # (a copy: autograd keeps the map until backward, the plan's buffer is overwritten by the next forward)
+                y1 = self._stem_map(x, pc_hm if self.isEarly else None, B, H, W, dev, sid).clone()
             self._stale = True
             feat = self._neck_nhwc(self._levels_nhwc(y1))
             return self._heads_train(feat, True, pc_hm, pc_dep, calib)

@@ -1562,6 +1562,155 @@ def max_pool2x2(x):
     return _NhwcToNchwFn.apply(max_pool2x2_nhwc(_to_nhwc(x)))
 
 
+# ---- the stem under autograd: the narrow convolution + BatchNorm + ReLU block (csrc/cf_stem_train.hip) ----
+def run_stem_conv_forward(x, weight, stride=1, radar=None):
+    """-> z (B,Ho,Wo,Cout) NHWC, the pre-BN map of a stem convolution (cf_stem_conv_forward, exact fp32 on the raw weight).
+    k = 7: x is the NCHW image and `radar` None or the (B,3,H/4,W/4) map that supplies the last three input channels;
+    k = 3: x is NHWC."""
+    N, Cin, k, _ = weight.shape
+    B, H, W = (x.shape[0], x.shape[2], x.shape[3]) if k == 7 else x.shape[:3]
+    ho, wo = conv_out_hw(H, W, k, stride)
+    z = torch.empty((B, ho, wo, N), device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().cf_stem_conv_forward(x.data_ptr(), _lib.ptr(radar), weight.data_ptr(), B, H, W, Cin, N, k, stride,
+                                                z.data_ptr(), _lib.stream_ptr()), "cf_stem_conv_forward")
+    return z
+
+
+def run_stem_conv_bwd_weight(gz, x, k, cin, stride=1, radar=None):
+    """-> gw (Cout,cin,k,k) of a stem convolution from gz (B,Ho,Wo,Cout) and its input as `run_stem_conv_forward` takes it
+    (cf_stem_conv_bwd_weight: slab partials added in slab order)."""
+    B, H, W = (x.shape[0], x.shape[2], x.shape[3]) if k == 7 else x.shape[:3]
+    N = gz.shape[-1]
+    gw = torch.empty((N, cin, k, k), device=x.device, dtype=torch.float32)
+    nbytes = _lib.load().cf_stem_conv_bwd_workspace_bytes(B, H, W, cin, N, k, stride)
+    ws = _bytes(nbytes, x.device)
+    _lib.check(_lib.load().cf_stem_conv_bwd_weight(gz.data_ptr(), x.data_ptr(), _lib.ptr(radar), B, H, W, cin, N, k, stride,
+                                                   gw.data_ptr(), ws.data_ptr(), nbytes, _lib.stream_ptr()), "cf_stem_conv_bwd_weight")
+    return gw
+
+
+def run_stem_conv_bwd_data(gz, weight, H, W, stride=1):
+    """-> gx (B,H,W,16) NHWC of a 3x3 stem convolution from gz (B,Ho,Wo,Cout) and the raw weight (cf_stem_conv_bwd_data)."""
+    B = gz.shape[0]
+    N, Cc, k, _ = weight.shape
+    gx = torch.empty((B, H, W, Cc), device=gz.device, dtype=torch.float32)
+    _lib.check(_lib.load().cf_stem_conv_bwd_data(gz.data_ptr(), weight.data_ptr(), B, H, W, Cc, N, k, stride, gx.data_ptr(),
+                                                 _lib.stream_ptr()), "cf_stem_conv_bwd_data")
+    return gx
+
+
+class _StemConvBnReluFn(torch.autograd.Function):
+    """`stem_conv_bn_relu` under autograd, in the style of `_ConvBnActFn`.  Saved: the block input (and the radar map), the pre-BN
+    map, the batch statistics, the raw weight.  Backward: cf_bn_act_backward, then cf_stem_conv_bwd_weight / cf_stem_conv_bwd_data
+    - each only when `needs_input_grad` asks for its output."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, radar, stats, stride, training, momentum, eps):
+        with torch.cuda.device(x.device):
+            x, wc, g, be = _f32c(x), _f32c(w), _f32c(gamma), _f32c(beta)
+            rad = None if radar is None else _f32c(radar)
+            z = run_stem_conv_forward(x, wc, stride, rad)
+            y, mean, invstd = run_bn_act_forward(z, g, be, stats[0], stats[1], training, momentum, eps, None, True)
+        ctx.training, ctx.stride, ctx.has_radar = bool(training), int(stride), rad is not None
+        ctx.save_for_backward(x, z, mean, invstd, wc, g, be, *([rad] if rad is not None else []))
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, z, mean, invstd, w, gamma, beta, *rest = ctx.saved_tensors
+        rad = rest[0] if rest else None
+        need_x, need_w, need_g, need_be = ctx.needs_input_grad[:4]
+        k, cin = w.shape[-1], w.shape[1]
+        gx = gw = None
+        with torch.cuda.device(x.device):
+            gy = _f32c(gy)
+            gz, _, gg, gbe = run_bn_act_backward(gy, z, gamma, beta, mean, invstd, ctx.training, None, True, need_x or need_w, False,
+                                                 need_g, need_be)
+            if need_w:
+                gw = run_stem_conv_bwd_weight(gz, x, k, cin, ctx.stride, rad)
+            if need_x:
+                gx = run_stem_conv_bwd_data(gz, w, x.shape[1], x.shape[2], ctx.stride)
+        return (gx, gw, gg, gbe, None, None, None, None, None, None)
+
+
+def _stem_check(who, x, nhwc, weight, bn_weight, bn_bias, running_mean, running_var, stride, radar):
+    """-> (Ho, Wo); x is (B,H,W,C) when `nhwc`, else (B,C,H,W)"""
+    for t in (x, weight, bn_weight, bn_bias, running_mean, running_var) + (() if radar is None else (radar,)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise NotImplementedError(f"{who}: float32 tensors only (no autocast, no fp16 / bf16 / float64)")
+    if x.dim() != 4 or weight.dim() != 4:
+        raise ValueError(f"{who}: x must be a 4-D map and weight (Cout,Cin,k,k)")
+    cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
+    if weight.shape[3] != k or not ((k == 7 and stride == 1 and 0 < cin <= 8) or (k == 3 and stride in (1, 2) and cin == 16)) \
+            or cout not in (16, 32):
+        raise NotImplementedError(f"{who}: weight must be (16 or 32, Cin, k, k) with k = 7 (stride 1, Cin <= 8) or k = 3 (stride 1 or 2, "
+                                  f"Cin = 16), padding (k-1)/2, one group - got {tuple(weight.shape)}, stride {stride!r}")
+    nhwc = nhwc and k == 3                                 # (the 7x7 layer reads the image as the caller holds it: NCHW planes)
+    B, cx, H, W = (x.shape[0], x.shape[3], x.shape[1], x.shape[2]) if nhwc else tuple(x.shape)
+    if radar is not None:
+        if k != 7 or cin <= 3 or H % 4 or W % 4:
+            raise NotImplementedError(f"{who}: a radar map goes with a 7x7 layer of more than 3 input channels on a map whose H, W are "
+                                      "multiples of 4")
+        if tuple(radar.shape) != (B, 3, H // 4, W // 4):
+            raise ValueError(f"{who}: radar must be {(B, 3, H // 4, W // 4)}, got {tuple(radar.shape)}")
+    if cx + (0 if radar is None else 3) != cin:
+        raise NotImplementedError(f"{who}: the input has {cx}{'' if radar is None else ' + 3'} channels, the weight {cin}")
+    if k == 7 and (x.requires_grad or (radar is not None and radar.requires_grad)) and torch.is_grad_enabled():
+        raise NotImplementedError(f"{who}: the 7x7 layer has no input gradient (nothing differentiates the image or the radar map); "
+                                  "detach the input")
+    for t, what in ((bn_weight, "bn_weight"), (bn_bias, "bn_bias"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if tuple(t.shape) != (cout,):
+            raise ValueError(f"{who}: {what} must be ({cout},), got {tuple(t.shape)}")
+    _need_cuda(x, weight, bn_weight, bn_bias, running_mean, running_var, radar)
+    return conv_out_hw(H, W, k, stride)
+
+
+def _stem_apply(x, B, ho, wo, weight, bn_weight, bn_bias, running_mean, running_var, stride, training, momentum, eps, radar):
+    if training and B * ho * wo == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {(B, weight.shape[0], ho, wo)}")
+    return _StemConvBnReluFn.apply(x, weight, bn_weight, bn_bias, radar, (running_mean, running_var), int(stride), bool(training),
+                                   float(momentum), float(eps))
+
+
+def stem_conv_bn_relu_nhwc(xn, weight, bn_weight, bn_bias, running_mean, running_var, stride=1, training=True, momentum=0.1,
+                           eps=1e-5, radar=None):
+    """`stem_conv_bn_relu` with an NHWC result and, for the 3x3 layers, an NHWC input: xn (B,H,W,16) -> (B,Ho,Wo,Cout).  The 7x7
+    layer still takes the NCHW image (and `radar`) as the caller holds it.  DLASeg.forward_stem_train composes the three layers
+    with it, without a layout launch in between."""
+    ho, wo = _stem_check("stem_conv_bn_relu", xn, True, weight, bn_weight, bn_bias, running_mean, running_var, stride, radar)
+    return _stem_apply(xn, xn.shape[0], ho, wo, weight, bn_weight, bn_bias, running_mean, running_var, stride, training, momentum, eps,
+                       radar)
+
+
+def stem_conv_bn_relu(x, weight, bn_weight, bn_bias, running_mean, running_var, stride=1, training=True, momentum=0.1, eps=1e-5,
+                      radar=None):
+    """One block of the reference's DLA-34 stem (model/networks/dla.py:193-203, 250-262: base_layer, level0, level1) as ONE operator
+    under autograd, on HIP kernels in both directions: Conv2d(k, stride, padding (k-1)/2, bias=False) -> BatchNorm2d -> ReLU on
+    narrow channel counts.  `x` (B,Cin,H,W) fp32 on the device -> (B,Cout,Ho,Wo); weight (Cout,Cin,k,k) with Cout 16 or 32 and
+    k = 7 (stride 1, Cin <= 8: base_layer) or k = 3 (stride 1 or 2, Cin = 16: level0, level1).  `radar` (k = 7 only): the
+    (B,3,H/4,W/4) map of early fusion; the kernels read it as input channels Cin-3 .. Cin-1 at (y >> 2, x >> 2) - what
+    F.interpolate(mode="nearest") + cat gives - and `x` then holds the other Cin - 3 channels.
+
+    Forward: cf_stem_conv_forward, exact fp32 on the raw weight - no packing, no range check, no host sync - then
+    cf_bn_act_train_forward.  `training=True`: batch statistics, running_mean / running_var updated in place as
+    torch.nn.BatchNorm2d does (num_batches_tracked is the caller's); one value per channel raises ValueError.
+    `training=False`: the affine of the running statistics, still differentiable.
+
+    Differentiable once in weight, bn_weight, bn_bias and - for k = 3 - x; only the launches `needs_input_grad` asks for run:
+    cf_bn_act_backward, then cf_stem_conv_bwd_weight and cf_stem_conv_bwd_data.  The 7x7 layer has no input gradient: an `x`
+    or `radar` that requires grad raises NotImplementedError.  Every result is bitwise reproducible (no float atomics).  CPU
+    tensors raise CfHipError, non-fp32 tensors and unsupported shapes NotImplementedError."""
+    ho, wo = _stem_check("stem_conv_bn_relu", x, False, weight, bn_weight, bn_bias, running_mean, running_var, stride, radar)
+    if weight.shape[2] == 7:
+        y = _stem_apply(x, x.shape[0], ho, wo, weight, bn_weight, bn_bias, running_mean, running_var, stride, training, momentum, eps,
+                        radar)
+    else:
+        y = _stem_apply(_to_nhwc(x), x.shape[0], ho, wo, weight, bn_weight, bn_bias, running_mean, running_var, stride, training,
+                        momentum, eps, None)
+    return _NhwcToNchwFn.apply(y)
+
+
 def maxpool2x2(x, out=None):
     _need_cuda(x)
     B, H, W, Cc = x.shape

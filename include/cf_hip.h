@@ -537,6 +537,29 @@ int cf_bn_act_backward(const float* gy, const float* x, const float* gamma, cons
  * element of gx is written, zeros included.  C a multiple of 4; no workspace. */
 int cf_maxpool2x2_bwd(const float* gout, const float* x, int B, int H, int W, int C, float* gx, void* stream);
 
+/* Training kernels of the DLA-34 stem (added within ABI 7: nothing existing changed): the narrow convolutions of
+ * base.base_layer (7x7, 3 or 6 -> 16), level0 (3x3, 16 -> 16) and level1 (3x3 stride 2, 16 -> 32), padding (k - 1) / 2,
+ * no bias, exact fp32, no float atomics (bitwise reproducible), 64-bit element offsets.  BatchNorm + ReLU on top of them
+ * are cf_bn_act_train_forward / cf_bn_act_backward (any C that is a multiple of 4).
+ *
+ * Geometry: k = 7 with stride 1 and Cin <= 8, or k = 3 with stride 1 or 2 and Cin = 16; Cout = 16 or 32;
+ * Ho = (H + 2 pad - k) / stride + 1.  weight is the raw torch [Cout][Cin][k][k]; z and gz are [B][Ho][Wo][Cout] NHWC.
+ * k = 7: x is the caller's NCHW image [B][Cin or Cin - 3][H][W]; radar NULL, or the [B][3][H/4][W/4] map that supplies
+ * the last three input channels, sampled at (y >> 2, x >> 2) inside the kernel (H, W multiples of 4).  k = 3: x is
+ * [B][H][W][16] NHWC and radar must be NULL.
+ * cf_stem_conv_forward: z, the pre-BN map.
+ * cf_stem_conv_bwd_weight: gw [Cout][Cin][k][k]; the output pixels are split into slabs whose partial sums (workspace:
+ * cf_stem_conv_bwd_workspace_bytes(...), 0 for a geometry outside the family) a second launch adds in slab order.
+ * cf_stem_conv_bwd_data: gx [B][H][W][16] of the 3x3 layers, plain stores of every element; under stride 2 a workgroup's
+ * pixels share their row / column parity.  The 7x7 layer has no input gradient (k = 7 is refused). */
+size_t cf_stem_conv_bwd_workspace_bytes(int B, int H, int W, int Cin, int Cout, int k, int stride);
+int cf_stem_conv_forward(const float* x, const float* radar, const float* weight, int B, int H, int W, int Cin, int Cout,
+                         int k, int stride, float* z, void* stream);
+int cf_stem_conv_bwd_weight(const float* gz, const float* x, const float* radar, int B, int H, int W, int Cin, int Cout,
+                            int k, int stride, float* gw, void* workspace, size_t workspace_bytes, void* stream);
+int cf_stem_conv_bwd_data(const float* gz, const float* weight, int B, int H, int W, int Cin, int Cout, int k, int stride,
+                          float* gx, void* stream);
+
 /* cf_upsample_dw: depthwise transposed conv (k = 2f, stride f, pad f/2, groups = C, no bias),
  * optionally fused with the IDA skip add:  out = convT(x) [+ skip].
  * replaces aten::conv_transpose2d + add of model/networks/dla.py:502-511, 518-524.

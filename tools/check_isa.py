@@ -20,6 +20,7 @@ SOURCES = {"cf_conv3x3_f16.hip": ("conv3x3_f16x3_kernel",), "cf_heads.hip": ("he
            "cf_dcn_bwd.hip": ("dcn_bwd_data_kernel", "dcn_bwd_weight_kernel"),
            "cf_neck_bwd.hip": ("conv3x3_bwd_data_kernel", "conv3x3_bwd_weight_kernel"),
            "cf_base_bwd.hip": ("conv_bwd_data_kernel", "conv_bwd_weight_kernel"),
+           "cf_stem_train.hip": ("stem_conv_fwd_kernel", "stem_conv_bwd_data_kernel", "stem_conv_bwd_weight_kernel"),
            "cf_targets.hip": ("targets_heat_kernel", "targets_frustum_kernel")}
 
 
@@ -63,7 +64,8 @@ NO_SCRATCH = ("head_patch16_kernel", "dcn_f16x3_kernel", "conv3x3_f16x3_kernel",
               "offmask_activate_kernel", "conv3x3_bwd_weight_kernel", "conv3x3_bwd_reduce_kernel", "conv3x3_bwd_data_kernel", "bn_stats_kernel",
               "bn_finalize_kernel", "bn_relu_apply_kernel", "bn_bwd_partial_kernel", "bn_bwd_finalize_kernel", "bn_bwd_apply_kernel",
               "upsample_bwd_x_kernel", "upsample_bwd_w_kernel", "upsample_bwd_reduce_kernel",
-              "conv_bwd_weight_kernel", "conv_bwd_reduce_kernel", "conv_bwd_data_kernel", "maxpool2x2_bwd_kernel")
+              "conv_bwd_weight_kernel", "conv_bwd_reduce_kernel", "conv_bwd_data_kernel", "maxpool2x2_bwd_kernel",
+              "stem_conv_fwd_kernel", "stem_conv_bwd_data_kernel", "stem_conv_bwd_weight_kernel", "stem_conv_bwd_reduce_kernel")
 
 
 def scratch_sizes(asm):
