@@ -17,8 +17,12 @@ from .detector import Detector
 from .loss import GenericLoss
 from .targets import PackedAnnotations, build_targets, pack_annotations
 from .train_inputs import AugmentParams, augment_images, draw_augmentation, flip_annotations
+from .optim import FusedAdamW, FusedSGD, configure_optimizers
+from .train import TrainStep
+from .checkpoint import loadModel, saveModel
 
-__all__ = ["AugmentParams", "augment_images", "draw_augmentation", "flip_annotations", "build_targets", "pack_annotations", "PackedAnnotations", "GenericLoss", "update_loss_weights", "Detector", "NuScenesResults", "convert_eval_format", "decode_post_packed", "preProcessImages", "radar_to_pc_dep", "CfgNode", "centerfusion_early_config", "centerfusion_middle_config", "centernet_config", "update_heads", "DLASeg",
+__all__ = ["FusedAdamW", "FusedSGD", "configure_optimizers", "TrainStep", "loadModel", "saveModel",
+           "AugmentParams", "augment_images", "draw_augmentation", "flip_annotations", "build_targets", "pack_annotations", "PackedAnnotations", "GenericLoss", "update_loss_weights", "Detector", "NuScenesResults", "convert_eval_format", "decode_post_packed", "preProcessImages", "radar_to_pc_dep", "CfgNode", "centerfusion_early_config", "centerfusion_middle_config", "centernet_config", "update_heads", "DLASeg",
            "getModel", "fusionDecode", "decode_packed", "unpack_detections", "DET_FIELDS",
            "DET_WIDTH", "getPcFrustumHeatmap", "getAffineTransform", "process_point_cloud_batch", "postProcess",
            "post_process_packed", "unpack_post", "POST_FIELDS", "POST_WIDTH"]

@@ -157,6 +157,24 @@ class TargetsArgs(C.Structure):
                 ("workspace", _f), ("workspace_bytes", C.c_size_t)]
 
 
+CF_OPTIM_CHUNK = 4096     # elements one workgroup of cf_optim_adamw / cf_optim_sgd owns (cf_optim_chunk_elems() of the library)
+
+
+class OptimTensor(C.Structure):
+    _fields_ = [("param", _f), ("grad", _f), ("state1", _f), ("state2", _f), ("numel", C.c_int64), ("step_base", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class OptimChunk(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("tensor", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptimArgs(C.Structure):
+    _fields_ = [("tensors", _f), ("chunks", _f), ("n_tensors", C.c_int32), ("n_chunks", C.c_int32), ("lr", C.c_double),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("wd", C.c_double), ("momentum", C.c_double),
+                ("decay", C.c_float), ("step", C.c_int32)]
+
+
 # every symbol include/cf_hip.h declares: (restype, argtypes)
 _i, _d = C.c_int, C.c_double
 SYMBOLS = {
@@ -192,6 +210,10 @@ SYMBOLS = {
     "cf_loss_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "cf_targets_build": (_i, [C.POINTER(TargetsArgs), _f]),
     "cf_targets_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "cf_optim_plan": (_i, [C.POINTER(OptimTensor), _i, C.POINTER(OptimChunk), C.c_int64, C.POINTER(C.c_int64)]),
+    "cf_optim_adamw": (_i, [C.POINTER(OptimArgs), _f]),
+    "cf_optim_sgd": (_i, [C.POINTER(OptimArgs), _f]),
+    "cf_optim_chunk_elems": (_i, []),
     "cf_head_train_forward": (_i, [C.POINTER(HeadTrainArgs), _f]),
     "cf_head_backward": (_i, [C.POINTER(HeadTrainArgs), _f]),
     "cf_head_train_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),

@@ -41,6 +41,7 @@ SOURCES = [
     ("cf_augment.hip", ["-ffp-contract=off"]),  # the fp32 colour chain rounds every operation, as torch's CPU kernels do
     ("cf_loss.hip", []),
     ("cf_targets.hip", ["-ffp-contract=off"]),
+    ("cf_optim.hip", ["-ffp-contract=off"]),    # AdamW / SGD round where torch's single-tensor CPU implementations do (the fused multiply-adds are written out)
     ("cf_pack.cpp", ["-ffp-contract=off"]),     # host-side packers: the fp32 BN fold must round like torch's (no fused multiply-add)
     ("cf_error.cpp", []),
 ]

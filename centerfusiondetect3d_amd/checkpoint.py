@@ -1,5 +1,5 @@
 """Checkpoint loading with the reference's legacy parameter names (model/model.py:47-250:
-`loadModel`, `elasticLoadStateDict`, `toggleWeightName`).
+`loadModel`, `elasticLoadStateDict`, `toggleWeightName`) and the epoch checkpoint of a training run (`saveModel`).
 
 Checkpoints of the original CenterFusion release and of earlier revisions of the reference name the
 heads `hm. / wh. / dep. / dim. / rot. / amodel_offset. / dep_sec. / rot_sec.` (v1) or by their bare new
@@ -84,8 +84,18 @@ def elastic_load_state_dict(model, state_dict, verbose=False):
     return model, report
 
 
+def saveModel(log, model, epoch, path):
+    """utils/utils.py:199-218: the model's `state_dict` (of `.module` behind a DataParallel wrapper) and `epoch` go into the log
+    dict, which is then written with `torch.save` - the file `loadModel` reads, with TRAIN.RESUME giving `epoch + 1`."""
+    inner = model.module if isinstance(model, torch.nn.DataParallel) else model
+    log["state_dict"] = inner.state_dict()
+    log["epoch"] = epoch
+    torch.save(log, path)
+
+
 def loadModel(model, config):
-    """model/model.py:137-166 for inference: -> (checkpoint, model, start_epoch)."""
+    """model/model.py:137-166 (without the optimiser half: optim.configure_optimizers rebuilds it from `start_epoch`):
+    -> (checkpoint, model, start_epoch)."""
     checkpoint = torch.load(config.MODEL.LOAD_DIR, map_location="cpu")
     start_epoch = 1
     if "epoch" in checkpoint and getattr(getattr(config, "TRAIN", None), "RESUME", False):

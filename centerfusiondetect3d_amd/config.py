@@ -34,13 +34,15 @@ def _base():
     c.DATASET = CfgNode(DATASET="nuscenes", RADAR_PC=True, MAX_PC=1000, MAX_PC_DIST=60.0,
                         PC_Z_OFFSET=0.0, PC_ROI_METHOD="pillars", PILLAR_DIMS=(1.5, 0.2, 0.2),
                         ONE_HOT_PC=False, NUM_CLASSES=10, PC_REVERSE=True)
-    c.MODEL = CfgNode(LOAD_DIR="", ARCH="dla_34", FREEZE_BACKBONE=False, NORM_EVAL=False,
+    c.MODEL = CfgNode(LOAD_DIR="", ARCH="dla_34", FREEZE_BACKBONE=False, NORM_EVAL=False, DEFREEZE=-1,
                       NORM_2D=False, FUSION_STRATEGY="middle", FRUSTUM=True, K=100,
                       INPUT_SIZE=(448, 800), OUTPUT_SIZE=(112, 200),
                       DLA=CfgNode(NODE="DeformConv"))
     c.LOSS_WEIGHTS = CfgNode(HEATMAP=1.0, AMODAL_OFFSET=1.0, DIMENSION_2D=0.1, DEPTH=1.0, DIMENSION_3D=1.0, ROTATION=1.0,
                              NUSCENES_ATT=1.0, VELOCITY=1.0, BBOX_2D=0.0, BBOX_3D=0.0, LIDAR_DEPTH=0.0, RADAR_DEPTH=0.0)
-    c.TRAIN = CfgNode(UNCERTAINTY_LOSS=False)
+    # optimizer and schedule as config/default.py:72-85 (optim.configure_optimizers, train.TrainStep)
+    c.TRAIN = CfgNode(UNCERTAINTY_LOSS=False, EPOCHS=60, WARM_EPOCHS=5, RESUME=False, OPTIMIZER="adam", LR=2.5e-4, LR_STEP=(50,),
+                      LR_SCHEDULER="StepLR")
     c.TEST = CfgNode(BATCH_SIZE=1)
     return c
 

@@ -2107,3 +2107,6 @@ def radar_ingest(pc, counts, intrinsics, img_wh, max_dist=60.0, z_offset=0.0, de
                                            int(bool(descending)), pc_2d.data_ptr(), pc_3d.data_ptr(), cnt.data_ptr(),
                                            _lib.stream_ptr()), "cf_radar_ingest")
     return pc_2d, pc_3d, cnt
+
+
+OPTIM_CHUNK = _lib.CF_OPTIM_CHUNK     # elements one workgroup of the optimizer kernels owns (CF_OPTIM_CHUNK of include/cf_hip.h; optim.py)

@@ -1002,6 +1002,59 @@ typedef struct cf_targets_args {
 int cf_targets_build(const cf_targets_args* a, void* stream);
 size_t cf_targets_workspace_bytes(int B, int M);
 
+/* cf_optim_adamw / cf_optim_sgd: the parameter update of a training step over ANY number of fp32 tensors in one launch
+ * (replaces torch.optim.AdamW / torch.optim.SGD as model/modelWithLoss.py:66-76 constructs them: on the order of a hundred
+ * foreach launches per step there).  Two DEVICE tables describe the work; they hold pointers and sizes only, so a host rebuilds
+ * them only when the set of (parameter, gradient) pointers changes:
+ *   tensors  [n_tensors] cf_optim_tensor: one record per parameter;
+ *   chunks   [n_chunks]  cf_optim_chunk: (tensor index, element offset); ONE workgroup of 256 threads owns one chunk of at most
+ *            CF_OPTIM_CHUNK elements of one tensor.  cf_optim_plan (host side) writes the list.
+ * Everything that changes from step to step travels by value in cf_optim_args.  A tensor's own step count is
+ * step - step_base (>= 1): torch keeps one count per parameter, and a parameter that receives its first gradient later starts at 1
+ * there - here its record carries the optimizer's count at the moment it joined.  No workgroup reads what another workgroup of
+ * the launch writes (no device-side counter), no LDS, no scratch.  16-byte accesses when all of a tensor's pointers are 16-byte
+ * aligned, 4-byte accesses otherwise and for the last numel % 4 elements.
+ * fp32 arithmetic in the order and with the roundings of torch's single-tensor CPU implementations (fma = one rounding, where
+ * torch's lerp_ / addcmul_ / add_(alpha) kernels fuse; every other operation rounds on its own):
+ *   AdamW  p *= decay (= 1 - lr * wd, rounded from double by the host);  m = fma(g - m, 1 - beta1, m);
+ *          v = fma((1 - beta2) * g, g, v * beta2);  bc1 = 1 - beta1^s, bc2 = 1 - beta2^s in double;
+ *          p += (-float(lr / bc1) * m) / (sqrt(v) / float(sqrt(bc2)) + eps)
+ *   SGD    g' = fma(wd, p, g);  buf = g' at the tensor's first step (s == 1), else momentum * buf + g';  p = fma(-lr, buf, p)
+ *          (no dampening, no Nesterov; state1 NULL = no momentum buffer: p = fma(-lr, g', p)). */
+#define CF_OPTIM_CHUNK 4096 /* elements per workgroup; a multiple of 4, so a chunk keeps its tensor's 16-byte alignment */
+typedef struct cf_optim_tensor {
+  float* param;
+  const float* grad;
+  float* state1;     /* AdamW: exp_avg;    SGD: momentum_buffer or NULL */
+  float* state2;     /* AdamW: exp_avg_sq; SGD: NULL                    */
+  int64_t numel;
+  int32_t step_base; /* the optimizer's step count before this tensor's first update */
+  int32_t reserved;  /* 0 */
+} cf_optim_tensor;
+typedef struct cf_optim_chunk {
+  int64_t offset;    /* first element of the chunk inside its tensor: a multiple of CF_OPTIM_CHUNK */
+  int32_t tensor;    /* index into the tensor table */
+  int32_t reserved;  /* 0 */
+} cf_optim_chunk;
+typedef struct cf_optim_args {
+  const cf_optim_tensor* tensors; /* device */
+  const cf_optim_chunk* chunks;   /* device */
+  int32_t n_tensors, n_chunks;
+  double lr;                      /* AdamW: divided by the bias correction in double, then rounded; SGD: rounded to fp32 */
+  double beta1, beta2, eps;       /* AdamW; 1 - beta is formed in double, then rounded, as Python does for torch */
+  double wd, momentum;            /* SGD */
+  float decay;                    /* AdamW: 1 - lr * wd, formed in double by the host */
+  int32_t step;                   /* the optimizer's step count INCLUDING this launch (>= 1) */
+} cf_optim_args;
+/* host side, no device access: the chunk list of `tensors` (HOST copy of the table: only numel is read) in table order, tensors
+ * with numel == 0 contributing none.  chunks == NULL: count only.  -> CF_OK with the number of chunks in *n_chunks; CF_EINVAL
+ * for a NULL table or n_chunks, n <= 0, a negative numel, or a `capacity` (entries of `chunks`) below the count. */
+int cf_optim_plan(const cf_optim_tensor* tensors, int n, cf_optim_chunk* chunks, int64_t capacity, int64_t* n_chunks);
+/* one launch each on `stream`; CF_EINVAL for NULL args / tables, n_tensors <= 0, n_chunks <= 0, step <= 0 */
+int cf_optim_adamw(const cf_optim_args* a, void* stream);
+int cf_optim_sgd(const cf_optim_args* a, void* stream);
+int cf_optim_chunk_elems(void); /* CF_OPTIM_CHUNK of the library */
+
 /* Weight packing runs once per load_state_dict (BatchNorm fold, slot tables, split hi / lo planes, MFMA fragment order).
  * For the f16x3 convolution and DCN operators it is part of this ABI (cf_pack_conv_f16x3, cf_pack_dcn_f16 above: host-side C,
  * byte-identical to the Python packers); the heads', the stem's and the upsample's weights are packed by
